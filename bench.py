@@ -15,7 +15,9 @@ its own HIP stream under the labelling of batch k+1) and step 03 of step i overl
 per rank, lecturemath_amd/sharded.py): every rank thresholds + labels its block, the packed CC records travel to rank 0 in
 one RCCL transfer per rank, rank 0 replays the matching and runs step 03; strong scaling, digests equal to N = 1.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the --steps steps, writes --dump-outputs and prints the line
+(`value`, `ms_per_step` and the in-region `roofline`).  --full adds the objects below that take work of their own (`parity`,
+`roofline.alone`, `cpu_baseline`, `fcn`, `e2e_rgb`; N > 1: `rgb_sharded`); without it they are null or absent.
   roofline      labelling launch sequence (lm_label_batch_logits), HBM bound: 8 B/px (4 B fp32 logit in + 4 B int32 label out; the
                 byte frame of SURVEY 8(d)'s 5 B/px figure is never materialised -- that accounting is printed beside it as
                 frac_survey_5Bpx) x W x H x frames per launch / mean launch duration, HIP events on the launching stream INSIDE the
@@ -27,6 +29,10 @@ Prints ONE JSON line (rank 0).  Extra objects:
   fcn           configs[1] measured in the same process: FCN-LectureNet forward at 1080p (ms/frame, algorithmic TFLOP/s,
                 max |logit - oracle|) and the CPU oracle's rate
   e2e_rgb       RGB frames -> FCN -> threshold -> ... -> step 03 -> reconstructed frames, frames/s
+
+--dump-outputs DIR: after the timed steps, what the last timed step computed -- the step 02 / 03 products and the reconstructed
+frames of its last batch (float64 / float32 .npy files, fixed seeded samples of the large ones, 64 MB at most; see dump_stream) --
+so that two builds can be compared output for output on identical inputs.
 """
 import argparse
 import ctypes
@@ -70,6 +76,11 @@ def parse():
     p.add_argument("--no-fcn-oracle", action="store_true", help="skip the CPU oracle forward pass (max |logit diff|, FCN cpu baseline)")
     p.add_argument("--workload", default="stream", choices=["stream", "fcn"],
                    help="stream = configs[2]/[3] (headline metric); fcn = configs[1] alone")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: parity digests, the labelling launches alone, the CPU baselines, "
+                        "`fcn` / `e2e_rgb` (N > 1: `rgb_sharded`); --cpu-frames, --fcn-frames, --e2e-frames and --no-fcn-oracle apply here")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     return p.parse_args()
 
 
@@ -110,7 +121,7 @@ def fcn_frame_size(H, W):
     return H, W
 
 
-def measure_fcn(a, lib, H, W, n_frames, with_oracle):
+def measure_fcn(a, lib, H, W, n_frames, with_oracle, warmup=2):
     import torch
     from lecturemath_amd import fcn, synth
     H, W = fcn_frame_size(H, W)      # configs[4]: the network always runs at <= 2.5 MP
@@ -120,7 +131,7 @@ def measure_fcn(a, lib, H, W, n_frames, with_oracle):
     eng.load_state_dict(sd)
     rgb, _ = synth.whiteboard_rgb(H, W, 1500, seed=20211)
     d_rgb = torch.from_numpy(rgb).cuda()
-    for _ in range(2):
+    for _ in range(warmup):
         out, text, rec = eng.forward(d_rgb)
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -173,6 +184,7 @@ def measure_fcn(a, lib, H, W, n_frames, with_oracle):
                                          "note": "random-init logits crowd the threshold; three seeds per assignment: profiles/r04_fcn_formats.json"}
         res["cpu_baseline"] = {"value": round(1.0 / cdt, 4), "unit": "frames/s", "cores": torch.get_num_threads(), "kind": "port",
                                "sample": "one 1080p frame, oracle/fcn.py (torch fp32 CPU restatement of FCN_lecturenet.py:260-403)"}
+    res["outputs"] = (out, text, rec)          # of the last timed forward pass (--dump-outputs); not part of the JSON line
     return res, eng, sd
 
 
@@ -261,7 +273,11 @@ def main_fcn(a):
     from lecturemath_amd import _lib
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     lib = _lib.load()
-    res, eng, _ = measure_fcn(a, lib, a.height, a.width, max(a.steps, 1), not a.no_fcn_oracle and a.cpu_frames > 0)
+    res, eng, _ = measure_fcn(a, lib, a.height, a.width, max(a.steps, 1), a.full and not a.no_fcn_oracle and a.cpu_frames > 0,
+                              warmup=max(a.warmup, 0))
+    out, text, rec = res.pop("outputs")
+    if a.dump_outputs:          # the logits, text and reconstruction heads of the last timed frame
+        write_dump(a.dump_outputs, {"logits": out.float().cpu().numpy(), "text": text.float().cpu().numpy(), "rec": rec.float().cpu().numpy()})
     fp32 = a.fcn_precision == "fp32"
     tfl = res["algorithmic_tflops"] if fp32 else res["executed_tflops"]
     peak = MFMA_F32_PEAK_TFLOPS if fp32 else MFMA_F16_PEAK_TFLOPS
@@ -273,7 +289,7 @@ def main_fcn(a):
                         "frac": round(tfl / peak, 4), "traffic": None, "launch_ms": res["ms_per_frame"],
                         "algorithmic_tflops": res["algorithmic_tflops"],
                         "note": "achieved counts executed MFMA flops (%s per algorithmic flop)" % (1 if fp32 else res["mfma_per_product"])},
-           "cpu_baseline": res.get("cpu_baseline"), "fcn": res}
+           "cpu_baseline": res.get("cpu_baseline"), "fcn": res, "full": a.full}
     print(json.dumps(out))
 
 
@@ -356,7 +372,7 @@ def main_sharded(a, torch, dist, lib, world, rank, rehearse, logits, gen_s):
                     e3.record(s_back)
                     rdone.record(s_back)
                     marks[-1] = marks[-1] + (e2, e3)
-                    info = {"scalars": [int(v) for v in gr.array("scalars")], "gs": gs, "gr": gr}
+                    info = {"scalars": [int(v) for v in gr.array("scalars")], "gs": gs, "gr": gr, "clean": clean}
         if gr is not None:
             rdone.synchronize()
         sh.finish()
@@ -388,7 +404,11 @@ def main_sharded(a, torch, dist, lib, world, rank, rehearse, logits, gen_s):
     lib.check(lib.lm_ctx_profile_read(sh.fs.labeler.ctx, ctypes.addressof(ms), ctypes.addressof(calls), ctypes.addressof(nfr)))
     fused = bool(lib.lm_label_was_fused(sh.fs.labeler.ctx))
     parity = None
-    if rank == sh.group_rank and info is not None:
+    if rank == sh.group_rank and info is not None and a.dump_outputs:
+        dump_stream(a.dump_outputs, info["gs"], info["gr"], info["clean"], None, F - ((F - 1) // B) * B)
+    if rank == sh.group_rank and info is not None and not a.full:
+        info["gr"].close()
+    elif rank == sh.group_rank and info is not None:
         dg = digests.from_device(info["gs"], info["gr"])
         k1 = info["gs"].counters()
         parity = {"digests": dg, "counters": {k: k1[k] for k in ("n_cc", "n_unique", "tempo_count")}, "n_groups": info["scalars"][2], "reference": None, "match": None}
@@ -403,7 +423,7 @@ def main_sharded(a, torch, dist, lib, world, rank, rehearse, logits, gen_s):
     sh.close()
     # the CPU baseline is a property of the workload, not of N: rank 0 times the oracle on the frames it holds (the other ranks wait in
     # the next collective), after the timed region
-    cpu = measure_cpu_baseline(logits, a.cpu_frames, 0, F, W, H) if rank == 0 and a.cpu_frames > 0 else None
+    cpu = measure_cpu_baseline(logits, a.cpu_frames, 0, F, W, H) if a.full and rank == 0 and a.cpu_frames > 0 else None
     del logits
     torch.cuda.empty_cache()
     seq0 = steps_all[0]["front_and_matching_ms"]
@@ -415,7 +435,7 @@ def main_sharded(a, torch, dist, lib, world, rank, rehearse, logits, gen_s):
 
     # ---------------- RGB frames -> FCN -> ... on every rank (weak scaling)
     rgb_res = None
-    if a.e2e_frames > 0:
+    if a.full and a.e2e_frames > 0:
         n_rank = a.e2e_frames
         n_tot = n_rank * world
         sd = synth.fcn_random_state_dict(synth.FCN_SHIPPED_WIDTHS, pixel_kernel=7, seed=0) if rank == 0 else None
@@ -464,7 +484,8 @@ def main_sharded(a, torch, dist, lib, world, rank, rehearse, logits, gen_s):
                "roofline": {"bound": "hbm", "kernel": "labelling launches of rank 0", "achieved": round(ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                             "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_note": traffic_note, "launch_ms": round(launch_ms, 4),
                             "launches": calls.value, "frames_per_launch": round(fpl, 2), "algorithmic_bytes_per_px": bpp},
-               "cpu_baseline": cpu, "parity": parity, "amdahl": amdahl, "per_rank_step_ms": steps_all, "rgb_sharded": rgb_res, "gen_seconds": round(gen_s, 2)}
+               "cpu_baseline": cpu, "parity": parity, "amdahl": amdahl, "per_rank_step_ms": steps_all, "rgb_sharded": rgb_res, "gen_seconds": round(gen_s, 2),
+               "full": a.full}
         print(json.dumps(out))
     dist.barrier()
     dist.destroy_process_group()
@@ -553,6 +574,53 @@ def measure_cpu_baseline(logits, n, first_frame, F, W, H):
                       "step 03 with all frames reconstructed %.1f s (oracle/grouping.py, numpy); single thread, host has %d cores"
                       % (first_frame + d0, first_frame + d0 + n, t1 - t0, t2 - t1, os.cpu_count()),
             "sparse_prefix": sparse, "reference_in_build_container": quoted}
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def sample_rows(a, cap, seed):
+    """A fixed, seeded subset of `cap` rows of `a`, kept in order; all of `a` when it has no more rows than that."""
+    if len(a) <= cap:
+        return a
+    return a[np.sort(np.random.default_rng(seed).choice(len(a), cap, replace=False))]
+
+
+def write_dump(d, arrays):
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_BUDGET_BYTES, "dump of %d bytes exceeds %d" % (total, DUMP_BUDGET_BYTES)
+    assert all(v.dtype in (np.float32, np.float64) for v in arrays.values())
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+
+
+def dump_stream(d, fs, gr, clean, labels, n_last):
+    """What one step of the stream path hands its caller, from the FrameStream / Grouping / buffers the step left: counters, CC records
+    (rec columns + unique index after the split), the step 03 tables, and the reconstructed frames (and int32 labels) of the last
+    batch.  Integers are written as float64 (exact); arrays longer than their cap are a fixed seeded sample of their rows."""
+    import torch
+    k = fs.counters()
+    r = fs.read(with_crops=False)
+    A = {n: gr.array(n) for n in ("ulist_off", "ulist_cc", "assign", "grp_off", "grp_members", "ages_off", "ages", "gpf_off", "gpf",
+                                  "bounds", "scalars")}
+    f64 = lambda v: np.ascontiguousarray(v, dtype=np.float64)  # noqa: E731
+    out = {"counters": f64([k[n] for n in ("n_frames", "n_cc", "n_crop_words", "n_unique", "n_active", "tempo_count")]),
+           "group_scalars": f64(A["scalars"]),
+           "frame_off": f64(sample_rows(r["frame_off"], 1 << 18, 1))}
+    rec = np.concatenate([r["rec"], A["assign"][:len(r["rec"])].reshape(-1, 1)], axis=1)
+    out["cc_records"] = f64(sample_rows(rec, 1 << 18, 2))                  # 9 columns
+    for i, n in enumerate(("ulist_off", "ulist_cc", "grp_off", "grp_members", "ages_off", "ages", "gpf_off", "gpf")):
+        out[n] = f64(sample_rows(A[n], 1 << 18, 10 + i))
+    out["group_bounds"] = f64(sample_rows(A["bounds"].reshape(-1, 4), 1 << 16, 20))
+    if clean is not None and n_last > 0:
+        c = clean[:n_last].reshape(-1)
+        idx = torch.from_numpy(np.sort(np.random.default_rng(30).choice(c.numel(), min(c.numel(), 1 << 20), replace=False))).to(c.device)
+        out["clean_last_batch_sample"] = c[idx].cpu().numpy().astype(np.float32)
+        out["clean_last_batch_sums"] = f64(clean[:n_last].reshape(n_last, -1).sum(dim=1, dtype=torch.int64).cpu().numpy())
+        if labels is not None:
+            out["labels_last_batch_sample"] = labels[:n_last].reshape(-1)[idx].cpu().numpy().astype(np.float32)
+    write_dump(d, out)
 
 
 def main():
@@ -802,8 +870,13 @@ def main():
     k1 = slots[0]["fs"].counters()
     assert k0 is None or k1 == k0, "steps are not reproducible: %r vs %r" % (k0, k1)
 
+    if a.dump_outputs:
+        last = slots[(a.steps - 1) % depth]
+        dump_stream(a.dump_outputs, last["fs"], last["gr"], last["clean"], labels, F - ((F - 1) // B) * B)
+    if not a.full:
+        close_groups()
     # ---- parity: digests of what the last timed step of every slot left, against the reference's digests of the same stream
-    used = slots[:min(depth, max(a.steps, 1))]
+    used = slots[:min(depth, max(a.steps, 1))] if a.full else []
     dg = [digests.from_device(sl["fs"], sl["gr"]) for sl in used if sl["gr"] is not None]
     sums = []
     if used and used[0]["gr"] is not None:
@@ -818,8 +891,9 @@ def main():
     def core(d):
         return {k: v for k, v in d.items() if k != "clean_frame_sums"}
 
-    parity = {"digests": dg[0] if dg else None, "all_slots_identical": all(core(d) == core(dg[0]) for d in dg),
-              "counters": {k: k1[k] for k in ("n_cc", "n_unique", "tempo_count")}, "reference": None, "match": None}
+    parity = None if not a.full else {
+        "digests": dg[0] if dg else None, "all_slots_identical": all(core(d) == core(dg[0]) for d in dg),
+        "counters": {k: k1[k] for k in ("n_cc", "n_unique", "tempo_count")}, "reference": None, "match": None}
     ref, gname = golden_digests(W, H, a.seed, F) if dg else (None, None)
     if ref:
         keys = [k for k in dg[0] if k in ref]
@@ -827,7 +901,7 @@ def main():
                                % (gname, F, "the oracle, itself pinned to the reference on the first 1,000 frames of the 1080p stream," if ref.get("produced_by") == "oracle" else "the reference"))
         parity["match"] = bool(all(dg[0][k] == ref[k] for k in keys) and ref["tempo_count"] == k1["tempo_count"] and ref["n_cc"] == k1["n_cc"])
         parity["compared"] = keys + ["tempo_count", "n_cc"]
-    if parity["match"] is False or not parity["all_slots_identical"]:
+    if parity is not None and (parity["match"] is False or not parity["all_slots_identical"]):
         sys.stderr.write("bench.py: digests differ (reference match: %r, slots identical: %r) -- the rate below is NOT a valid result\n"
                          % (parity["match"], parity["all_slots_identical"]))
         if os.environ.get("LM_BENCH_STRICT"):
@@ -836,7 +910,7 @@ def main():
     # the same launch sequence once more with nothing else in flight (after the timed region): in the pipeline, kernels of the
     # matching stream share the GPU with it
     alone_ms = None
-    if world == 1 and not os.environ.get("LM_BENCH_NO_ALONE"):
+    if a.full and world == 1 and not os.environ.get("LM_BENCH_NO_ALONE"):
         close_groups()
         sl = slots[0]
         lib.check(lib.lm_ctx_set_profiling(sl["fs"].labeler.ctx, 1))
@@ -884,7 +958,7 @@ def main():
                                   "source": "profiles/r03_s2_operating_points.txt (round 3's library on one lease; not re-measured by this run)"}}
 
     # ---- CPU baseline (the checker, timed after the timed region; rank 0 only)
-    cpu = measure_cpu_baseline(logits, a.cpu_frames, 0, F, W, H) if a.cpu_frames > 0 else None
+    cpu = measure_cpu_baseline(logits, a.cpu_frames, 0, F, W, H) if a.full and a.cpu_frames > 0 else None
 
     out = {
         "metric": "frames/sec end-to-end binarize+CC+group @1080p", "value": round(F * a.steps / dt, 2), "unit": "frames/s",
@@ -902,14 +976,15 @@ def main():
                    "schedule": {"gated": "lm_stream_run_logits schedule 1: labelling launches kept apart from the matching's wide kernels",
                                 "free": "lm_stream_run_logits schedule 0: matching of a batch behind its records on its own queue, nothing kept apart",
                                 "gated-py": "Python-driven gated loop"}.get(schedule, schedule)},
-        "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "gen_seconds": round(gen_s, 2),
+        "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "gen_seconds": round(gen_s, 2), "full": a.full,
     }
-    if world == 1 and a.fcn_frames > 0:
+    if a.full and world == 1 and a.fcn_frames > 0:
         del logits
         for sl in slots:
             sl["fs"].close()
         torch.cuda.empty_cache()
         res, eng, fsd = measure_fcn(a, lib, H, W, a.fcn_frames, not a.no_fcn_oracle)
+        res.pop("outputs")
         out["fcn"] = res
         if a.e2e_frames > 0:
             out["e2e_rgb"] = measure_e2e_rgb(a, lib, eng, H, W, a.e2e_frames, sd=fsd)

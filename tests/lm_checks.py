@@ -448,30 +448,25 @@ def check_render_wraparound(lib):
     assert {0, 253, 254, 255} <= values, values
 
 
-def reference_c_library():
-    """oracle/_ref/accessmath_lib.so: the reference's own C file compiled by oracle/Makefile (travels to the GPU box)."""
-    import ctypes
-    path = os.path.join(ROOT, "oracle", "_ref", "accessmath_lib.so")
-    if not os.path.exists(path):
-        import pytest
-        pytest.skip("oracle/_ref/accessmath_lib.so not built (reference sources absent)")
-    return ctypes.CDLL(path)
-
-
-def check_legacy_exports(lib, big=False):
+def legacy_cases(L, big=False):
     """The classical-binarizer exports of accessmath_lib.c (speaker_detection_handle_frame, regionCumulativeDistribution,
-    adapthisteq, combine_results) vs the reference C library itself, bit for bit (float64 outputs compared as bit patterns)."""
+    adapthisteq, combine_results) of the ctypes library `L` on fixed inputs: yields (case, result), where an output array is
+    given by the sha256 of its bytes (float64 outputs: their bit patterns) and speaker_detection_handle_frame by its return value
+    and the bit patterns of its three outputs.  tests/golden/make_golden_reference_checks.py stores what the reference C library
+    returns (tests/golden/g14_legacy_exports.json)."""
     import ctypes
-    ref, mine = reference_c_library(), lib.cdll
+    import hashlib
+
+    def digest(a):
+        return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
     rng = np.random.default_rng(17)
     vp, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-    for L in (ref, mine):
-        L.regionCumulativeDistribution.restype = None
-        L.regionCumulativeDistribution.argtypes = [vp, ci, ci, ci, ci, ci, ci, cd, vp]
-        L.adapthisteq.argtypes = [vp, ci, ci, cd, ci, ci, vp]
-        L.combine_results.argtypes = [vp, vp, ci, ci, ctypes.c_ubyte, vp]
-        L.speaker_detection_handle_frame.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]
-        L.speaker_detection_handle_frame.restype = ci
+    L.regionCumulativeDistribution.restype = None
+    L.regionCumulativeDistribution.argtypes = [vp, ci, ci, ci, ci, ci, ci, cd, vp]
+    L.adapthisteq.argtypes = [vp, ci, ci, cd, ci, ci, vp]
+    L.combine_results.argtypes = [vp, vp, ci, ci, ctypes.c_ubyte, vp]
+    L.speaker_detection_handle_frame.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]
+    L.speaker_detection_handle_frame.restype = ci
     sizes = [(97, 131), (64, 64)] + ([(1080, 1920)] if big else [])
     for h, w in sizes:
         # smooth image + noise so that histograms are neither flat nor degenerate
@@ -480,40 +475,40 @@ def check_legacy_exports(lib, big=False):
         gray = np.ascontiguousarray(gray)
         # -- regionCumulativeDistribution
         for (x0, x1, y0, y1), slope in (((0, w - 1, 0, h - 1), 0.0), ((3, w // 2, 5, h - 2), 0.01), ((w // 3, w // 3, 0, 0), 0.02)):
-            outs = []
-            for L in (ref, mine):
-                o = np.zeros(256, np.float64)
-                L.regionCumulativeDistribution(gray.ctypes.data, w, h, x0, x1, y0, y1, slope, o.ctypes.data)
-                outs.append(o)
-            assert (outs[0].view(np.int64) == outs[1].view(np.int64)).all()
+            o = np.zeros(256, np.float64)
+            L.regionCumulativeDistribution(gray.ctypes.data, w, h, x0, x1, y0, y1, slope, o.ctypes.data)
+            yield "%dx%d regionCumulativeDistribution %d %d %d %d %r" % (h, w, x0, x1, y0, y1, slope), digest(o.view(np.int64))
         # -- adapthisteq
         for gx, gy, slope in ((8, 8, 0.01), (3, 5, 0.0), (1, 1, 0.02), (2, 1, 0.005)):
-            outs = []
-            for L in (ref, mine):
-                o = np.zeros((h, w), np.uint8)
-                L.adapthisteq(gray.ctypes.data, w, h, slope, gx, gy, o.ctypes.data)
-                outs.append(o)
-            assert (outs[0] == outs[1]).all(), (h, w, gx, gy, slope, int((outs[0] != outs[1]).sum()))
+            o = np.zeros((h, w), np.uint8)
+            L.adapthisteq(gray.ctypes.data, w, h, slope, gx, gy, o.ctypes.data)
+            yield "%dx%d adapthisteq %d %d %r" % (h, w, gx, gy, slope), digest(o)
         # -- combine_results
         board = rng.integers(0, 256, (h, w), dtype=np.uint8)
         for thr in (0, 97, 255):
-            outs = []
-            for L in (ref, mine):
-                o = np.zeros((h, w), np.uint8)
-                L.combine_results(board.ctypes.data, gray.ctypes.data, w, h, thr, o.ctypes.data)
-                outs.append(o)
-            assert (outs[0] == outs[1]).all()
+            o = np.zeros((h, w), np.uint8)
+            L.combine_results(board.ctypes.data, gray.ctypes.data, w, h, thr, o.ctypes.data)
+            yield "%dx%d combine_results %d" % (h, w, thr), digest(o)
         # -- speaker_detection_handle_frame
         f0 = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
         f1 = f0.copy()
         f1[h // 4:h // 2, w // 3:w // 3 + 20] = rng.integers(0, 256, (h // 2 - h // 4, 20, 3), dtype=np.uint8)
-        for a, b, thr, jump in ((f1, f0, 20, 1), (f1, f0, 20, 4), (f0, f0, 20, 2), (f1, f0, 300, 1)):
-            outs = []
-            for L in (ref, mine):
-                bd, av, dv = np.zeros(4), np.zeros(2), np.zeros(2)
-                n = L.speaker_detection_handle_frame(a.ctypes.data, b.ctypes.data, w, h, 3, thr, jump, bd.ctypes.data, av.ctypes.data, dv.ctypes.data)
-                outs.append((n, bd.view(np.int64).tolist(), av.view(np.int64).tolist(), dv.view(np.int64).tolist()))
-            assert outs[0] == outs[1], (h, w, thr, jump, outs)
+        for k, (a, b, thr, jump) in enumerate(((f1, f0, 20, 1), (f1, f0, 20, 4), (f0, f0, 20, 2), (f1, f0, 300, 1))):
+            bd, av, dv = np.zeros(4), np.zeros(2), np.zeros(2)
+            n = L.speaker_detection_handle_frame(a.ctypes.data, b.ctypes.data, w, h, 3, thr, jump, bd.ctypes.data, av.ctypes.data, dv.ctypes.data)
+            yield "%dx%d speaker_detection_handle_frame %d" % (h, w, k), [n, bd.view(np.int64).tolist(), av.view(np.int64).tolist(), dv.view(np.int64).tolist()]
+
+
+def check_legacy_exports(lib, big=False):
+    """The classical-binarizer exports of this library vs what the reference C library itself returns on the same inputs
+    (tests/golden/g14_legacy_exports.json), bit for bit."""
+    import json
+    gold = json.load(open(os.path.join(GOLD, "g14_legacy_exports.json")))
+    n = 0
+    for case, got in legacy_cases(lib.cdll, big):
+        assert got == gold[case], case
+        n += 1
+    assert n == (42 if big else 28), n
 
 
 def check_fcn_golden(lib, name, tol=1e-3, precision="f16x3", require_planar=False, formats=None):

@@ -85,7 +85,7 @@ def test_stream_churn_and_empty_frames(hip_lib, oracle_built):
 
 def test_legacy_exports_vs_reference_c(hip_lib, oracle_built):
     """speaker_detection_handle_frame / regionCumulativeDistribution / adapthisteq / combine_results of accessmath_lib.c on
-    the device vs the reference C library (oracle/_ref), bit for bit, up to 1080p."""
+    the device vs what the reference C library returns (tests/golden/g14_legacy_exports.json), bit for bit, up to 1080p."""
     lm_checks.check_legacy_exports(hip_lib, big=True)
 
 

@@ -1,8 +1,7 @@
 """CPU: the drop-in layer (reference module paths / script entry points) on the emulated library."""
+import io
 import os
 import pickle
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -40,49 +39,62 @@ def test_fcn_class(emu_lib):
     dropin_checks.check_fcn_class(emu_lib, worker=False)       # the worker: test_step01_entry_points below
 
 
-REF = "/root/reference/ACCESS2021_release"
+class _Held:
+    """Stand-in for a class of the reference's modules while unpickling: keeps the pickled state as it is."""
+
+    def __setstate__(self, state):
+        self.state = state
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference only exists in the build container")
-def test_pickle_interop_with_reference(emu_lib, tmp_path):
-    """Our step-02 pickle is consumed by the REFERENCE's step 03 (its own classes, in a separate interpreter), and the
-    reference's step-02 pickle by our step 03: both must reproduce the golden group ages."""
+class _StateUnpickler(pickle.Unpickler):
+    def find_class(self, module, name):
+        if module.split(".")[0] in ("AccessMath", "AM_CommonTools"):
+            return type(name, (_Held,), {"module": module})
+        return super().find_class(module, name)
+
+
+def _same(a, b, path):
+    """Equal pickled state: same types, same values (numpy scalars and arrays by dtype and value)."""
+    if isinstance(a, _Held) or isinstance(b, _Held):
+        assert type(a).__name__ == type(b).__name__ and a.module == b.module, path
+        if type(a).__name__ != "IntervalIndex":         # an index of the active list, rebuilt from it by whoever reads it
+            _same(a.state, b.state, path + "." + type(a).__name__)
+        return
+    assert type(a) is type(b), (path, type(a), type(b))
+    if isinstance(a, dict):
+        assert sorted(a) == sorted(b), (path, sorted(a), sorted(b))
+        for k in a:
+            _same(a[k], b[k], "%s[%r]" % (path, k))
+    elif isinstance(a, (list, tuple)):
+        assert len(a) == len(b), path
+        for k, (x, y) in enumerate(zip(a, b)):
+            _same(x, y, "%s[%d]" % (path, k))
+    elif isinstance(a, np.ndarray):
+        assert a.dtype == b.dtype and a.shape == b.shape and (a == b).all(), path
+    else:
+        assert a == b, (path, a, b)
+
+
+def test_pickle_interop_with_reference(emu_lib):
+    """Our step-02 pickle carries the state the REFERENCE's step 02 pickles where the reference's step 03 reads it (same classes,
+    attributes, types and values, so that step reads from it what it reads from its own), and the reference's step-02 pickle
+    (tests/golden/g13_ref_step02_short_gap_jitter.pkl.gz, tests/golden/make_golden_reference_checks.py) is consumed by our step 03:
+    both must reproduce the golden group ages."""
+    import gzip
     blob = dropin_checks.check_steps_02_03(emu_lib, "short_gap_jitter")
-    (tmp_path / "ours.dat").write_bytes(blob)
-    code = r'''
-import sys, pickle, io, contextlib, json
-sys.path.insert(0, "%s"); sys.path.insert(0, "%s")
-import ref_env; ref_env.enter()
-from AccessMath.preprocessing.content.cc_stability_estimator import CCStabilityEstimator
-t, i, est = pickle.load(open("%s", "rb"))
-assert type(est).__module__ == "AccessMath.preprocessing.content.cc_stability_estimator"
-with contextlib.redirect_stdout(io.StringIO()):
-    est.split_stable_cc_by_gaps(4, 3)
-    stable = est.get_stable_cc_idxs(3)
-    tov, tot, aov = est.compute_overlapping_stable_cc(stable, 5)
-    groups, gid = est.compute_groups(stable, tov, 0.5, None, None)
-    ages, gpf = est.compute_groups_temporal_information(groups)
-print(json.dumps([ages[k] for k in range(len(groups))]))
-# and the other direction: a reference-made step-02 pickle
-import numpy as np
-sys.path.insert(0, "%s")
-import lm_checks
-g, spec, frames = lm_checks.load_stream("short_gap_jitter")
-e2 = CCStabilityEstimator(spec["w"], spec["h"], 0.85, 0.85, spec["gap2"], False)
-for f in frames: e2.add_frame(f, True)
-e2.finish_processing = None
-pickle.dump((t, i, e2), open("%s", "wb"), protocol=pickle.HIGHEST_PROTOCOL)
-''' % (os.path.join(dropin_checks.ROOT, "tests", "golden"), dropin_checks.ROOT, tmp_path / "ours.dat",
-       os.path.join(dropin_checks.ROOT, "tests"), tmp_path / "theirs.dat")
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=str(tmp_path))
-    assert out.returncode == 0, out.stderr[-2000:]
-    import json
+    with gzip.open(os.path.join(lm_checks.GOLD, "g13_ref_step02_short_gap_jitter.pkl.gz"), "rb") as fh:
+        theirs = fh.read()
+    ours_state, theirs_state = (_StateUnpickler(io.BytesIO(b)).load() for b in (blob, theirs))
+    assert type(ours_state[2]).__name__ == "CCStabilityEstimator" and ours_state[2].module == "AccessMath.preprocessing.content.cc_stability_estimator"
+    # what the reference's step 03 reads of the estimator (pre_ST3D_v3.0_03_cc_grouping.py:41-91 and the methods it calls,
+    # cc_stability_estimator.py:166-681) -- the rest is add_frame's working state
+    step03 = ("width", "height", "unique_cc_objects", "unique_cc_frames", "cc_idx_per_frame", "tempo_count")
+    _same(ours_state[:2], theirs_state[:2], "times/indices")
+    _same({k: ours_state[2].state[k] for k in step03}, {k: theirs_state[2].state[k] for k in step03}, "estimator")
     g, spec, frames = lm_checks.load_stream("short_gap_jitter")
-    ages_ref = json.loads(out.stdout.strip().splitlines()[-1])
-    assert [[(a,) for a in lst] for lst in ages_ref] == lm_checks.unrag(g["ages"], g["ages_off"])
     # reference's pickle -> our step 03
     dropin_checks.use_library(emu_lib)
-    t, i, est = pickle.loads((tmp_path / "theirs.dat").read_bytes())
+    t, i, est = pickle.loads(theirs)
     assert type(est).__module__ == "AccessMath.preprocessing.content.cc_stability_estimator" and hasattr(est, "_imported")
     s03 = dropin_checks.load_script("pre_ST3D_v3.0_03_cc_grouping.py")
     rec, conf, st3d = s03.process_input(dropin_checks.fake_process({"CC_STABILITY_MAX_GAP": str(spec["gap3"])}), (t, i, est))

@@ -1,82 +1,96 @@
-"""Container-only (skipped where /root/reference is absent): the drop-in boundary under the reference's OWN name.  The library
-built from this repository's sources (here the CPU emulation build: there is no GPU in the build container; on a GPU box the
-same symlink points at liblecturemath_hip.so) is installed as ./accessmath_lib.so and the UNMODIFIED
-reference labeler (AccessMath/preprocessing/content/labeler.py:24 CDLL('./accessmath_lib.so'), :138-168 CC_AgeBoundaries) runs
-extractSpatioTemporalContent on the G1 frames: kept CCs, boxes, sizes and crops must equal the golden file the reference produced
-with its own C library."""
+"""The drop-in boundary under the reference's OWN name.  The library built from this repository's sources (here the CPU emulation
+build; on a GPU box the same symlink points at liblecturemath_hip.so) is installed as ./accessmath_lib.so
+and loaded the way the reference labeler loads it (AccessMath/preprocessing/content/labeler.py:24 CDLL('./accessmath_lib.so')),
+CC_AgeBoundaries is declared and called with the reference's own argument types and arguments (:138-168) on the G1 frames, and the
+six arrays it returns -- and the kept CCs, boxes, sizes and crops the labeler builds from them (:175-192) -- must equal the golden file
+the reference produced with its own C library."""
 import os
 import subprocess
 import sys
 
 import numpy as np
-import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "golden"))
-import ref_env  # noqa: E402
-
-pytestmark = pytest.mark.skipif(not ref_env.available(), reason="needs the reference (build container only)")
+GOLD = os.path.join(HERE, "golden")
 
 CHILD = r"""
 import os, sys, ctypes
 import numpy as np
-sys.dont_write_bytecode = True
-sys.path.insert(0, %(shims)r); sys.path.insert(0, %(ref)r)
-import warnings; warnings.filterwarnings("ignore")
-from AccessMath.preprocessing.content.labeler import Labeler          # the reference's module, loads ./accessmath_lib.so
-assert os.path.realpath(Labeler.accessmath_lib._name) == os.path.realpath(%(lib)r), Labeler.accessmath_lib._name
-assert Labeler.accessmath_lib.lm_abi_version() == 1        # it IS this repository's library
+lib = ctypes.CDLL(os.path.abspath('./accessmath_lib.so'))
+assert os.path.realpath(lib._name) == os.path.realpath(%(lib)r), lib._name
+lib.lm_abi_version.restype = ctypes.c_int32
+assert lib.lm_abi_version() == 1                            # it IS this repository's library
+i32p, f32p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+lib.CC_AgeBoundaries.argtypes = [i32p, f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, i32p, i32p, i32p, i32p, i32p, f32p]
+lib.CC_AgeBoundaries.restype = ctypes.c_int32
 g = np.load(%(gold)r)
 total = 0
 for i in range(int(g["n"])):
-    img = g["img%%d" %% i]
-    ccs = Labeler.extractSpatioTemporalContent(img, np.zeros(img.shape, np.float32))
-    rec = np.asarray([(c.cc_id, c.min_x, c.max_x, c.min_y, c.max_y, c.size) for c in ccs], np.int32).reshape(-1, 6)
+    img, labels = g["img%%d" %% i], np.ascontiguousarray(g["labels%%d" %% i], np.int32)
+    n = int(g["n%%d" %% i])
+    if n == 0:
+        assert len(g["rec%%d" %% i]) == 0, i
+        continue
+    ages = np.zeros(img.shape, np.float32)
+    out = [np.zeros(n, np.int32) for _ in range(5)] + [np.zeros(n, np.float32)]
+    lib.CC_AgeBoundaries(labels.ctypes.data_as(i32p), ages.ctypes.data_as(f32p), img.shape[1], img.shape[0], n,
+                         *[o.ctypes.data_as(f32p if o.dtype == np.float32 else i32p) for o in out])
+    mins_y, maxs_y, mins_x, maxs_x, counts, min_ages = out
+    assert (np.stack(out[:5]) == g["stats%%d" %% i]).all(), i
+    assert (min_ages == g["ages%%d" %% i]).all(), i
+    keep = [c for c in range(n) if counts[c] >= 20]                       # Labeler.MIN_CC_PIXELS
+    rec = np.asarray([(c, mins_x[c], maxs_x[c], mins_y[c], maxs_y[c], counts[c]) for c in keep], np.int32).reshape(-1, 6)
     assert (rec == g["rec%%d" %% i]).all(), i
-    crops = np.concatenate([c.img.ravel() for c in ccs]) if ccs else np.zeros(0, np.uint8)
-    assert (crops == g["crops%%d" %% i]).all(), i
-    total += len(ccs)
-print("reference labeler over this library ok:", total, "CCs")
+    crops = [((labels[mins_y[c]:maxs_y[c] + 1, mins_x[c]:maxs_x[c] + 1] == c + 1).astype(np.uint8) * 255).ravel() for c in keep]
+    flat = np.concatenate(crops) if crops else np.zeros(0, np.uint8)
+    assert flat.shape == g["crops%%d" %% i].shape and (flat == g["crops%%d" %% i]).all(), i
+    total += len(keep)
+print("reference labeler boundary over this library ok:", total, "CCs")
 """
 
 
 def test_reference_labeler_runs_on_this_library(emu_lib, tmp_path):
     lib = os.path.join(HERE, "hipemu", "liblecturemath_emu.so")
     os.symlink(lib, tmp_path / "accessmath_lib.so")
-    src = CHILD % {"shims": os.path.join(HERE, "golden", "_ref_shims"), "ref": ref_env.REF_ROOT, "lib": lib,
-                   "gold": os.path.join(HERE, "golden", "g1_label.npz")}
+    src = CHILD % {"lib": lib, "gold": os.path.join(GOLD, "g1_label.npz")}
     r = subprocess.run([sys.executable, "-c", src], cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "reference labeler over this library ok" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
+    assert r.returncode == 0 and "reference labeler boundary over this library ok" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
 
 
-def test_interval_index_find_matches_vs_reference():
-    """dropin IntervalIndex.find_matches (a sweep of its own) against the reference's (tools/interval_index.py:42-99) on random
-    interval sets: the same pairs; both return them in the order of their own sweep over start positions, so
-    both are compared as sorted lists (every caller on the path sorts or set-intersects them: cc_stability_estimator.py:78-90)."""
-    import importlib.util
-
-    def load(name, path):
-        spec = importlib.util.spec_from_file_location(name, path)
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        return mod
-    ref = load("lm_ref_interval_index", os.path.join(ref_env.REF_ROOT, "AccessMath/preprocessing/tools/interval_index.py"))
-    mine = load("lm_dropin_interval_index", os.path.join(os.path.dirname(HERE), "lecturemath_amd/dropin/AccessMath/preprocessing/tools/interval_index.py"))
+def interval_trials(index_cls):
+    """The random interval sets (300 trials) as pairs of filled `index_cls` instances; tests/golden/make_golden_reference_checks.py
+    runs the same trials through the reference's IntervalIndex."""
     rng = np.random.default_rng(5)
     for trial in range(300):
         n, m = int(rng.integers(0, 40)), int(rng.integers(0, 40))
         span = int(rng.choice([5, 30, 200]))
 
-        def fill(idx_cls, count, seed):
+        def fill(count, seed):
             r2 = np.random.default_rng(seed)
-            idx = idx_cls(True)
+            idx = index_cls(True)
             for k in range(count):
                 a = int(r2.integers(0, span))
                 b = a + int(r2.integers(1, max(2, span // 3)))
                 idx.add(a, b, k)
             return idx
-        pairs = []
-        for cls in (ref.IntervalIndex, mine.IntervalIndex):
-            a, b = fill(cls, n, 2 * trial), fill(cls, m, 2 * trial + 1)
-            pairs.append(sorted((int(x), int(y)) for x, y in a.find_matches(b)))
-        assert pairs[0] == pairs[1], trial
+        yield fill(n, 2 * trial), fill(m, 2 * trial + 1)
+
+
+def test_interval_index_find_matches_vs_reference():
+    """dropin IntervalIndex.find_matches (a sweep of its own) against the reference's (tools/interval_index.py:42-99) on random
+    interval sets, whose pairs are stored in tests/golden/g11_interval_index.npz: the same pairs; both return them in the order of
+    their own sweep over start positions, so both are compared as sorted lists (every caller on the path sorts or set-intersects
+    them: cc_stability_estimator.py:78-90)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(
+        "lm_dropin_interval_index", os.path.join(os.path.dirname(HERE), "lecturemath_amd/dropin/AccessMath/preprocessing/tools/interval_index.py"))
+    mine = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mine)
+    g = np.load(os.path.join(GOLD, "g11_interval_index.npz"))
+    off, ref_pairs = g["off"], g["pairs"]
+    n = 0
+    for trial, (a, b) in enumerate(interval_trials(mine.IntervalIndex)):
+        got = sorted((int(x), int(y)) for x, y in a.find_matches(b))
+        assert got == [tuple(int(v) for v in p) for p in ref_pairs[off[trial]:off[trial + 1]]], trial
+        n += 1
+    assert n == len(off) - 1 == 300

@@ -4,11 +4,11 @@ cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp; O=$GRAFT_REPO_ROOT/gpurun_out/final2;
 python -m pytest tests -x -q -m gpu 2>&1 | tail -3 > $O/gpu_tests.txt; cat $O/gpu_tests.txt
 grep -q passed $O/gpu_tests.txt || exit 1
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r02_bench_driver_like.json 2> $O/bench.err; echo "bench rc=$?"
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r02_bench_driver_like.json 2> $O/bench.err; echo "bench rc=$?"
 LM_BENCH_SCHEDULE=free python bench.py --gpus 1 --steps 6 --warmup 2 --fcn-frames 0 --cpu-frames 0 > $O/r02_bench_free.json 2>/dev/null
 python bench.py --gpus 1 --steps 6 --warmup 2 --depth 1 --fcn-frames 0 --cpu-frames 0 > $O/r02_bench_depth1.json 2>/dev/null
 LM_BENCH_REHEARSE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 2 --warmup 1 --cpu-frames 0 --fcn-frames 0 > $O/r02_bench_rehearse_n2.json 2> $O/rehearse.err; echo "rehearse rc=$?"
-for p in f16x3 f16x2 f16 fp32; do python bench.py --workload fcn --steps 20 --fcn-precision $p > $O/r02_fcn_precision_ladder_$p.json 2>/dev/null; done
+for p in f16x3 f16x2 f16 fp32; do python bench.py --full --workload fcn --steps 20 --fcn-precision $p > $O/r02_fcn_precision_ladder_$p.json 2>/dev/null; done
 python tools/label_microbench.py 64 1080 1920 5000 > $O/r02_label_microbench.txt 2>&1
 python tools/label_microbench.py 64 1080 1920 192 >> $O/r02_label_microbench.txt 2>&1
 cd /tmp

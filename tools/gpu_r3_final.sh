@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp; O=$GRAFT_REPO_ROOT/gpurun_out/r3final; mkdir -p $O
 timeout -k 10 1100 python -m pytest tests -x -q -m gpu > $O/r03_final_gpu_tests.txt 2>&1; echo "pytest rc=$?"; tail -3 $O/r03_final_gpu_tests.txt
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-timeout -k 10 700 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r03_final_bench_driver_like.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 700 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r03_final_bench_driver_like.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python3 - <<'PY'
 import json
 d=json.load(open('gpurun_out/r3final/r03_final_bench_driver_like.json'))

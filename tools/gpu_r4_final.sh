@@ -2,7 +2,7 @@
 # round 4, final evidence with the final code: the driver's bench invocation, its kernel stats, FCN per layer + MFMA-pipe counters + formats,
 # the 4K line, the two-rank rehearsal started by bench.py itself
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp; O=$GRAFT_REPO_ROOT/gpurun_out/r4final; mkdir -p $O; R=$GRAFT_REPO_ROOT
-timeout -k 10 700 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r04_final_bench_driver_like.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 700 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r04_final_bench_driver_like.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python3 - $O/r04_final_bench_driver_like.json <<'PY'
 import json, sys
 d=json.load(open(sys.argv[1]))
@@ -22,9 +22,9 @@ cd $R
 python3 tools/fcn_mfma_pmc.py $(ls $O/m/*/*counter_collection.csv | head -1) $O/r04_final_fcn_mfma_pmc_mixed.json | tail -2; rm -rf $O/m
 timeout -k 10 600 python tools/fcn_formats.py $O/r04_final_fcn_formats.json 3 30 "only=mixed;r3-mixed (all six f16x3);px2=a2;planar-f16" > $O/r04_final_fcn_formats.txt 2>&1 || { tail -20 $O/r04_final_fcn_formats.txt; exit 1; }
 grep -v amdgpu.ids $O/r04_final_fcn_formats.txt | tail -4
-timeout -k 10 600 python bench.py --height 2160 --width 3840 --frames 1024 --batch 16 --steps 5 --warmup 4 --fcn-frames 20 --e2e-frames 32 > $O/r04_final_4k_bench.json 2> $O/b4k.err || { tail -20 $O/b4k.err; exit 1; }
+timeout -k 10 600 python bench.py --full --height 2160 --width 3840 --frames 1024 --batch 16 --steps 5 --warmup 4 --fcn-frames 20 --e2e-frames 32 > $O/r04_final_4k_bench.json 2> $O/b4k.err || { tail -20 $O/b4k.err; exit 1; }
 python3 -c "
 import json; d=json.load(open('$O/r04_final_4k_bench.json')); print('4K value', d['value'], 'parity', d['parity']['match'], 'frac', d['roofline']['frac'], 'alone', d['roofline']['alone']['frac'], 'traffic', d['roofline']['traffic'], 'e2e', d['e2e_rgb'].get('value'))"
-LM_BENCH_REHEARSE=1 timeout -k 10 400 python bench.py --gpus 2 --frames 1024 --steps 3 --warmup 2 --e2e-frames 8 > $O/r04_final_bench_rehearse_n2.json 2> $O/rehearse.err || { tail -20 $O/rehearse.err; exit 1; }
+LM_BENCH_REHEARSE=1 timeout -k 10 400 python bench.py --full --gpus 2 --frames 1024 --steps 3 --warmup 2 --e2e-frames 8 > $O/r04_final_bench_rehearse_n2.json 2> $O/rehearse.err || { tail -20 $O/rehearse.err; exit 1; }
 python3 -c "
 import json; d=json.load(open('$O/r04_final_bench_rehearse_n2.json')); print('N=2 rehearsal: value', d['value'], 'parity', d['parity'] and d['parity']['match'], 'cpu', d['cpu_baseline'] and d['cpu_baseline']['value'], 'traffic', d['roofline']['traffic'], 'rgb', d['rgb_sharded'] and d['rgb_sharded']['value'])"

@@ -21,7 +21,7 @@ timeout -k 10 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --out
 cd $R
 python3 tools/fcn_mfma_pmc.py $(ls $O/m/*/*counter_collection.csv | head -1) $O/r04_4k_fcn_mfma_pmc_mixed.json | tail -30
 rm -rf $O/m
-timeout -k 10 600 python bench.py --height 2160 --width 3840 --frames 1024 --batch 16 --steps 5 --warmup 4 --fcn-frames 20 --e2e-frames 32 > $O/r04_4k_bench.json 2> $O/b4k.err || { tail -20 $O/b4k.err; exit 1; }
+timeout -k 10 600 python bench.py --full --height 2160 --width 3840 --frames 1024 --batch 16 --steps 5 --warmup 4 --fcn-frames 20 --e2e-frames 32 > $O/r04_4k_bench.json 2> $O/b4k.err || { tail -20 $O/b4k.err; exit 1; }
 python3 - $O/r04_4k_bench.json <<'PY'
 import json, sys
 d=json.load(open(sys.argv[1]))

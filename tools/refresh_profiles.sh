@@ -6,8 +6,8 @@ R=$(pwd)
 O=$R/gpurun_out/final
 mkdir -p $O
 export TMPDIR=/tmp
-python bench.py > $O/bench.log 2>&1 && grep '^{"metric' $O/bench.log > $O/r01_final_bench.json
-python bench.py --no-pipeline > $O/bench_np.log 2>&1 && grep '^{"metric' $O/bench_np.log > $O/r01_final_bench_nopipeline.json
+python bench.py --full > $O/bench.log 2>&1 && grep '^{"metric' $O/bench.log > $O/r01_final_bench.json
+python bench.py --full --no-pipeline > $O/bench_np.log 2>&1 && grep '^{"metric' $O/bench_np.log > $O/r01_final_bench_nopipeline.json
 python tools/label_microbench.py 64 > $O/r01_final_label_microbench.txt 2>&1
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $O/p_bench -- python3 $R/bench.py --steps 6 --cpu-frames 0 > $O/p_bench.log 2>&1
