@@ -295,6 +295,35 @@ int lm_fcn2_set_layer(LmFcn2* f, int layer, const int32_t* desc, int ndesc, cons
 /* same contract as lm_fcn_forward */
 int lm_fcn2_forward(LmFcn2* f, const uint8_t* d_rgb, int h, int w, float* d_out, float* d_text, float* d_rec, void* stream);
 
+/* ====================================================================================================
+ * PNG hand-off codec (csrc/lm_png.hip): 8-bit grayscale, non-interlaced PNG files of width x height frames, encoded and
+ * decoded on the device -- the compressed_frames / CC_RECONSTRUCTED_OUTPUT lists the step scripts pass along
+ * (FCN_lecturenet_binarizer.py:56, helper.py:31, cc_stability_estimator.py:678).
+ * ==================================================================================================== */
+#define LM_PNG_OK 0
+#define LM_PNG_UNSUPPORTED 1   /* valid PNG of another colour type / bit depth / interlace: decode it on the host */
+#define LM_PNG_CORRUPT 2       /* malformed file, wrong IHDR size, bad zlib stream or adler32 */
+
+typedef struct LmPng LmPng;
+/* Codec for frames of width x height (width <= 16384, height * (width + 1) <= 4e8), batches of up to max_batch (<= 1024) files.
+ * Device scratch is allocated on the first encode / decode. */
+LmPng* lm_png_create(int width, int height, int max_batch);
+void lm_png_destroy(LmPng* p);
+/* Bytes of one encoder output slot: the largest file lm_png_encode writes for this size (a multiple of 16); 0 for bad sizes. */
+int64_t lm_png_encode_bound(int width, int height);
+/* d_frames: device uint8 [n][height][width], any byte values.  File i is written to d_out + i * capacity (capacity >=
+ * lm_png_encode_bound, a multiple of 4; d_out 4-byte aligned), its size to d_sizes[i] (device int64).  Every row is
+ * Up-filtered and coded as literals and distance-1 matches in one fixed-Huffman deflate block. */
+int lm_png_encode(LmPng* p, const uint8_t* d_frames, int n, uint8_t* d_out, int64_t capacity, int64_t* d_sizes, void* stream);
+/* Copies file i (d_sizes[i] bytes at d_slots + i * capacity) to d_dst + d_offsets[i]; all pointers device. */
+int lm_png_pack(const uint8_t* d_slots, int64_t capacity, const int64_t* d_sizes, const int64_t* d_offsets, int n, uint8_t* d_dst, void* stream);
+/* File i: d_lengths[i] bytes at d_files + d_offsets[i] (device).  Frame i goes to d_frames + i * width * height, its status
+ * (LM_PNG_*) to d_status[i] (device int32); a frame whose status is not LM_PNG_OK holds unspecified bytes.  Stored, fixed and
+ * dynamic deflate blocks, IDAT split over any number of chunks, all five row filters.  Checks the zlib header and adler32,
+ * not the chunk CRCs.  Never reads outside a file's [offset, offset + length) nor writes outside its frame. */
+int lm_png_decode(LmPng* p, const uint8_t* d_files, const int64_t* d_offsets, const int64_t* d_lengths, int n, uint8_t* d_frames,
+                  int32_t* d_status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_PATH = os.path.join(_HERE, "liblecturemath_hip.so")
 
 LM_OK, LM_ERR_ARG, LM_ERR_HIP, LM_ERR_CAPACITY, LM_ERR_STATE = 0, 1, 2, 3, 4
+LM_PNG_OK, LM_PNG_UNSUPPORTED, LM_PNG_CORRUPT = 0, 1, 2
 
 
 class LecturemathLibraryError(RuntimeError):
@@ -91,6 +92,12 @@ SIGNATURES = {
     "lm_fcn2_destroy": (None, [_vp]),
     "lm_fcn2_set_layer": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _i64, ctypes.c_int, _vp, ctypes.c_int]),
     "lm_fcn2_forward": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "lm_png_create": (_vp, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "lm_png_destroy": (None, [_vp]),
+    "lm_png_encode_bound": (_i64, [ctypes.c_int, ctypes.c_int]),
+    "lm_png_encode": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _i64, _vp, _vp]),
+    "lm_png_pack": (ctypes.c_int, [_vp, _i64, _vp, _vp, ctypes.c_int, _vp, _vp]),
+    "lm_png_decode": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _vp, _vp, _vp]),
 }
 
 

@@ -10,7 +10,7 @@ import numpy as np
 
 from AM_CommonTools.data.connected_component import ConnectedComponent
 from AccessMath.preprocessing.tools.interval_index import IntervalIndex
-from lecturemath_amd import device, png
+from lecturemath_amd import device, png, png_device
 
 _LAZY = ("unique_cc_objects", "unique_cc_frames", "cc_idx_per_frame", "cc_int_index_x", "cc_int_index_y", "cc_last_frame",
          "cc_active", "tempo_count", "img_idx")
@@ -239,13 +239,20 @@ class CCStabilityEstimator:
 
     def frames_from_groups(self, cc_groups, group_boundaries, groups_per_frame, group_ages, group_images, save_prefix=None,
                            stable_min_frames=3, show_unstable=True):
+        return self._frames_png(png_device.codec())
+
+    def _frames_png(self, codec):
+        """the reconstructed frames as PNG files, encoded by host zlib or (codec 'device') on the device"""
         g = self._cur(getattr(self, "_thr", 0.5))
         n = self.img_idx
         out = []
         for f0 in range(0, n, self.BATCH):
             m = min(self.BATCH, n - f0)
-            for frame in g.be.to_host(g.render(f0, m)):
-                out.append(png.encode_gray8(frame))
+            if codec == "device":
+                out.extend(png_device.encode_gray8_device(g.render(f0, m), lib=g.lib))
+            else:
+                for frame in g.be.to_host(g.render(f0, m)):
+                    out.append(png.encode_gray8(frame))
         return out
 
     def frames_from_groups_device(self, first, count):

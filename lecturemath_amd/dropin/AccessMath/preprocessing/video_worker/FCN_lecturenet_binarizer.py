@@ -1,9 +1,10 @@
 """Step-01 video worker with the reference's protocol (video_worker/FCN_lecturenet_binarizer.py:30-79):
 initialize(w, h) / handleFrame(frame, last_frame, v_index, abs_time, rel_time, abs_frame_idx) / getWorkName() / finalize(),
-results in frame_times, frame_indices, compressed_frames (PNG byte arrays).  No OpenCV: BGR->RGB is a slice, PNG is zlib."""
+results in frame_times, frame_indices, compressed_frames (PNG byte arrays).  No OpenCV: BGR->RGB is a slice, PNG is zlib
+(LM_PNG_CODEC=device: the PNG is encoded on the device, lecturemath_amd.png_device)."""
 import PIL.Image
 
-from lecturemath_amd import png
+from lecturemath_amd import png, png_device
 
 
 class FCN_LectureNet_Binarizer:
@@ -33,7 +34,10 @@ class FCN_LectureNet_Binarizer:
         binary, text_mask, rec_img = self.lecture_net.binarize(pil_image, return_others=True, force_binary=True)
         binary = 255 - binary                                              # ink = 255 from here on
         self.last_binary, self.last_text, self.last_rec = binary, text_mask, rec_img
-        self.compressed_frames.append(png.encode_gray8(binary))
+        if png_device.codec() == "device":
+            self.compressed_frames.append(png_device.encode_gray8_device(binary)[0])
+        else:
+            self.compressed_frames.append(png.encode_gray8(binary))
         self.frame_indices.append(abs_frame_idx)
         self.frame_times.append(abs_time)
         if self.debug_mode and self.debug_start <= abs_time <= self.debug_end:

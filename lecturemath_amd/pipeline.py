@@ -5,12 +5,14 @@ the device unless asked for).
     pipe = LecturePipeline(1920, 1080, conf={...reference config keys...}, network=fcn_or_None)
     pipe.add_rgb_frames(rgb_u8, times, indices)        # FCN -> threshold -> invert -> label/records/matching
     pipe.add_binary_frames(binary_u8, times, indices)  # already binarized input (ink = 255)
+    pipe.add_png_frames(pngs, times, indices)          # a step-01 pickle's compressed_frames, decoded on the device
     out = pipe.finish()                                # grouping, video segmentation, keyframes
 
 The stages are the drop-in classes and scripts themselves (lecturemath_amd/dropin: CCStabilityEstimator,
 pre_ST3D_v3.0_03/04/05 process_input), so every product is the one the step-by-step scripts give; only the hand-offs differ
 (add_frames_device / no PNG).  `out` holds: group_ages, conflicts, st3d (SpaceTimeStruct), intervals, keyframes, cc_times,
-and -- lazily, on request -- the reconstructed frames as PNG byte strings like the reference's CC_RECONSTRUCTED_OUTPUT."""
+and -- lazily, on request -- the reconstructed frames as PNG byte strings like the reference's CC_RECONSTRUCTED_OUTPUT
+(finish(reconstructed_png=True): host zlib; "device": encoded on the device, lecturemath_amd.png_device)."""
 import importlib.util
 import os
 import sys
@@ -70,6 +72,14 @@ class LecturePipeline:
         self.estimator.add_frames_device(frames)
         self._stamp(int(frames.shape[0]), times, indices)
 
+    def add_png_frames(self, pngs, times=None, indices=None):
+        """list of 8-bit grayscale PNG files of the pipeline's size, ink = 255 (a step-01 pickle's compressed_frames): decoded on
+        the device (lecturemath_amd.png_device) a batch at a time and fed to step 02 without leaving HBM."""
+        from lecturemath_amd import png_device
+        for b0 in range(0, len(pngs), png_device.BATCH):
+            self.estimator.add_frames_device(png_device.decode_gray8_device(pngs[b0:b0 + png_device.BATCH], self.width, self.height, self.lib))
+        self._stamp(len(pngs), times, indices)
+
     def add_rgb_frames(self, rgb, times=None, indices=None):
         """uint8 [n, H, W, 3]: FCN-LectureNet logits -> sigmoid * 255 >= threshold -> inverted binary (ink = 255), all on the device
         (FCN_lecturenet.py:452-467 + FCN_lecturenet_binarizer.py:54), then step 02."""
@@ -91,6 +101,7 @@ class LecturePipeline:
 
     # ---- steps 03, 04, 05 ----------------------------------------------------------------------------------------------
     def finish(self, reconstructed_png=False):
+        """reconstructed_png: False (none), True (host zlib, whatever LM_PNG_CODEC says) or "device" (encoded on the device)."""
         from AccessMath.data.space_time_struct import SpaceTimeStruct
         est, cfg = self.estimator, self.configuration
         est.finish_processing()
@@ -104,8 +115,7 @@ class LecturePipeline:
         conflicts = est.compute_conflicting_groups(stable, all_ov, len(groups), gid)
         group_images, group_boundaries = est.compute_group_images(groups, group_ages, cfg.get_float("CC_GROUPING_MIN_IMAGE_THRESHOLD", 0.5))
         st3d = SpaceTimeStruct(self.frame_times, self.frame_indices, est.height, est.width, group_ages, group_images, group_boundaries)
-        compressed = (est.frames_from_groups(groups, group_boundaries, groups_per_frame, group_ages, group_images, None, min_times, True)
-                      if reconstructed_png else [])
+        compressed = est._frames_png("device" if reconstructed_png == "device" else "host") if reconstructed_png else []
         step03 = [(self.frame_times, self.frame_indices, compressed), (group_ages, conflicts), st3d]
         import contextlib
         import io
