@@ -148,7 +148,7 @@ extern "C" void lm_ctx_destroy(LmCtx* c)
     if (!c) return;
     lm_profile_free(c);
     void* ptrs[] = {c->bits, c->starts, c->prefix, c->rowoff, c->rowcnt, c->band_runs, c->band_base, c->band_roots, c->band_fallback, c->parent, c->final_label,
-                    c->n_labels, c->rootbits, c->wordprefix, c->mid_sync, c->st_min_y, c->st_max_y, c->st_min_x, c->st_max_x, c->st_count, c->kept_label,
+                    c->n_labels, c->rootbits, c->wordprefix, c->st_min_y, c->st_max_y, c->st_min_x, c->st_max_x, c->st_count, c->kept_label,
                     c->kept_cropoff, c->frame_kept, c->frame_cropwords, c->stage_u8, c->stage_i32, c->stage_f32};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -169,7 +169,6 @@ extern "C" LmCtx* lm_ctx_create(int width, int height, int max_batch)
     c->g.H = height;
     c->g.WW = (width + 63) / 64;
     c->band_rows = (c->g.WW > 32) ? 16 : LM_BAND_ROWS_MAX;
-    if (const char* e = getenv("LM_BAND_ROWS")) { const int v = atoi(e); if (v == 8 || v == 16 || v == 32 || v == 64) c->band_rows = v; }      // tuning experiments
     c->nbands = (height + c->band_rows - 1) / c->band_rows;
     c->slot = ((c->band_rows * ((width + 1) / 2)) + 63) & ~63;       // worst-case runs of one band, multiple of 64
     c->g.cap = c->nbands * c->slot;
@@ -200,7 +199,6 @@ extern "C" LmCtx* lm_ctx_create(int width, int height, int max_batch)
     rc |= lm_alloc(&c->kept_cropoff, BC);
     rc |= lm_alloc(&c->frame_kept, (size_t)max_batch);
     rc |= lm_alloc(&c->frame_cropwords, (size_t)max_batch);
-    rc |= lm_alloc(&c->mid_sync, 2 * (1 + 2 * (size_t)max_batch));
     if (rc != LM_OK) {
         lm_ctx_destroy(c);
         return nullptr;
@@ -279,56 +277,35 @@ struct LmLabelSrc {
     const float* logits; float edge; unsigned flip; uint8_t* d_binary_out;
 };
 
-// runs of a band's union-find forest kept in LDS: 4,096 (16 KB) for bands of up to 32 rows, 8,192 for 64-row bands
-static inline int lm_band_lds_runs(int band_rows) { return band_rows > 32 ? 2 * LM_BAND_LDS : LM_BAND_LDS; }
+// dynamic LDS of lm_k_band: the band's bit rows, run starts and prefixes (18 B per 64-px word), a forest of LM_BAND_LDS runs,
+// row offsets and run counts
+static inline size_t lm_band_smem(const LmCtx* c) { return (size_t)c->band_rows * c->g.WW * 18 + (size_t)LM_BAND_LDS * 4 + (65 + 64) * 4 + 64; }
 
-// phase: 0 = the whole sequence, 1 = the row packing only, 2 = everything behind it
-static int lm_label_launch(LmCtx* c, const LmLabelSrc& src, int f0, int n, int32_t* d_labels, hipStream_t st, int phase = 0)
+static int lm_label_launch(LmCtx* c, const LmLabelSrc& src, int f0, int n, int32_t* d_labels, hipStream_t st)
 {
     const uint8_t* d_binary = src.d_binary;
     const LmGeom g = c->g;
     const int nbands = c->nbands, slot = c->slot;
     const int capw = g.cap / 64;
-    const int band_lds = lm_band_lds_runs(c->band_rows);
-    const size_t band_smem = (size_t)c->band_rows * g.WW * 18 + (size_t)band_lds * 4 + (65 + 64) * 4 + 64;
     const unsigned long long magic_ww = ((1ull << 40) / (unsigned)g.WW) + 1;
     const long long R = (long long)n * g.H;
     const size_t px = (size_t)g.W * g.H, r0 = (size_t)f0 * g.H, w0 = r0 * g.WW, b0 = (size_t)f0 * nbands, c0 = (size_t)f0 * g.cap, cw0 = (size_t)f0 * capw;
-    if (phase == 2) goto rest;
     if (src.logits)
         hipLaunchKernelGGL(lm_k_pack_rows_logits, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, src.logits + f0 * px, src.edge, src.flip,
                            src.d_binary_out ? src.d_binary_out + f0 * px : nullptr, c->bits + w0, c->starts + w0, c->prefix + w0, c->rowcnt + r0, g.W, g.WW, R);
     else
         hipLaunchKernelGGL(lm_k_pack_rows, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, d_binary + f0 * px, c->bits + w0, c->starts + w0, c->prefix + w0,
                            c->rowcnt + r0, g.W, g.WW, R);
-    if (phase == 1) { LM_HIP(hipGetLastError()); return LM_OK; }
-rest:
-    static const int band_threads = [] { const char* e = getenv("LM_BAND_THREADS"); const int v = e ? atoi(e) : 512; return (v == 128 || v == 256 || v == 512) ? v : 512; }();
-    hipLaunchKernelGGL(lm_k_band, dim3(nbands, n), dim3(band_threads), band_smem, st, c->bits + w0, c->starts + w0, c->prefix + w0, c->rowcnt + r0,
+    hipLaunchKernelGGL(lm_k_band, dim3(nbands, n), dim3(512), lm_band_smem(c), st, c->bits + w0, c->starts + w0, c->prefix + w0, c->rowcnt + r0,
                        c->rowoff + r0, c->band_runs + b0, c->parent + c0, c->band_fallback + b0, g.H, g.WW, slot, g.cap, lm_debug_band_phases(), magic_ww,
-                       c->band_rows, f0 == 0 ? lm_debug_band_stamps(nbands, n) : nullptr, band_lds);
+                       c->band_rows, f0 == 0 ? lm_debug_band_stamps(nbands, n) : nullptr, LM_BAND_LDS);
     const LmStatInit si = {c->st_min_y + c0, c->st_max_y + c0, c->st_min_x + c0, c->st_max_x + c0, c->st_count + c0, g.W, g.H};
-    static const int fused_middle = [] { const char* e = getenv("LM_LABEL_FUSED_MIDDLE"); return e ? atoi(e) : LM_LABEL_FUSED_MIDDLE_DEFAULT; }();
-#if !LM_HIP_EMULATED
-    if (fused_middle) {
-        // seam unions, flatten + flags, numbering in one launch with two per-frame rendezvous (lm_k_middle).  Two counter sets: part 0 (on
-        // `st`) uses set 0, the other part (on the aux queue) set 1; each launch zeroes its set first and passes base values of 0
-        // (lm_label_batch caps the parts at two while this switch is on)
-        unsigned* sync = c->mid_sync + (size_t)(f0 ? 1 : 0) * (1 + 2 * (size_t)c->max_batch);
-        LM_HIP(hipMemsetAsync(sync, 0, (1 + 2 * (size_t)n) * sizeof(unsigned), st));
-        hipLaunchKernelGGL(lm_k_middle, dim3((unsigned)nbands * n), dim3(256), 0, st, c->bits + w0, c->starts + w0, c->prefix + w0, c->rowoff + r0,
-                           c->band_fallback + b0, c->parent + c0, c->band_runs + b0, c->rootbits + cw0, c->wordprefix + cw0, c->band_roots + b0,
-                           c->band_base + b0, c->n_labels + f0, c->final_label + c0, g.WW, g.H, g.cap, c->band_rows, slot, capw, nbands, sync, 0u, 0u, si);
-    } else
-#endif
-    {
     hipLaunchKernelGGL(lm_k_seam_union, dim3(nbands, n), dim3(256), 0, st, c->bits + w0, c->starts + w0, c->prefix + w0, c->rowoff + r0,
                        c->band_fallback + b0, c->parent + c0, g.WW, g.H, g.cap, c->band_rows);
     hipLaunchKernelGGL(lm_k_flatten_flag, dim3(nbands, n), dim3(256), 0, st, c->parent + c0, c->band_runs + b0, c->rootbits + cw0, c->wordprefix + cw0,
                        c->band_roots + b0, slot, g.cap, capw);
     hipLaunchKernelGGL(lm_k_apply_labels, dim3(nbands, n), dim3(256), 0, st, c->parent + c0, c->band_runs + b0, c->rootbits + cw0, c->wordprefix + cw0,
                        c->band_roots + b0, c->band_base + b0, c->n_labels + f0, c->final_label + c0, slot, g.cap, capw, si);
-    }
     if (d_labels) {
         const unsigned Q = (unsigned)(g.W + 3) / 4;
         const unsigned long long magic_q = ((1ull << 40) / Q) + 1;       // lm_fastdiv: exact for H * Q < 2^24
@@ -360,17 +337,13 @@ static int lm_label_batch_src(LmCtx* c, const LmLabelSrc& src, int n_frames, int
     {
         // per call: the attribute belongs to the (function, device) pair and the call is cheap; a process-wide "already configured"
         // flag would skip it on a second device or race between caller threads
-        const size_t band_smem = (size_t)c->band_rows * g.WW * 18 + (size_t)lm_band_lds_runs(c->band_rows) * 4 + (65 + 64) * 4 + 64;
-        LM_HIP(hipFuncSetAttribute((const void*)lm_k_band, hipFuncAttributeMaxDynamicSharedMemorySize, (int)band_smem));
+        LM_HIP(hipFuncSetAttribute((const void*)lm_k_band, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm_band_smem(c)));
     }
 #endif
     if (lm_profile_mark(c, st, true, n_frames)) return LM_ERR_HIP;
     static const int want_parts = [] { const char* e = getenv("LM_LABEL_PARTS"); const int v = e ? atoi(e) : LM_LABEL_PARTS; return (v >= 1 && v <= 8) ? v : LM_LABEL_PARTS; }();
     int parts = want_parts;
     while (parts > 1 && n_frames / parts < LM_LABEL_PART_MIN) parts--;
-    // the experimental fused middle (LM_LABEL_FUSED_MIDDLE=1) has two rendezvous counter sets, one per queue: a third part would share
-    // a set with a part running concurrently on the other queue (its memset zeroing counters workgroups spin on)
-    if (parts > 2 && getenv("LM_LABEL_FUSED_MIDDLE") && atoi(getenv("LM_LABEL_FUSED_MIDDLE"))) parts = 2;
     if (parts > 1 && !c->aux_stream) {
         LM_HIP(hipStreamCreateWithFlags((hipStream_t*)&c->aux_stream, hipStreamNonBlocking));
         LM_HIP(hipEventCreateWithFlags((hipEvent_t*)&c->ev_fork, hipEventDisableTiming));
@@ -381,28 +354,15 @@ static int lm_label_batch_src(LmCtx* c, const LmLabelSrc& src, int n_frames, int
         if (rc) return rc;
     } else {
         hipStream_t aux = (hipStream_t)c->aux_stream;
-        // Two parts are STAGGERED: the second part starts when the first has packed its rows, so its packing (bandwidth bound) runs under
-        // the first part's band / seam / numbering kernels (latency bound) and the first part's label writer under the second's middle.
-        // Started together the halves ran in step -- both packings, both middles, both writers -- and nothing overlapped.
-        static const int stagger = [] { const char* e = getenv("LM_LABEL_STAGGER"); return e ? atoi(e) : 0; }();
-        int rc = LM_OK;
-        const int n0 = n_frames / parts + (n_frames % parts ? 1 : 0);
-        const bool stag = stagger && parts == 2;
-        if (stag) rc = lm_label_launch(c, src, 0, n0, d_labels, st, 1);
-        if (rc) return rc;
         LM_HIP(hipEventRecord((hipEvent_t)c->ev_fork, st));
         LM_HIP(hipStreamWaitEvent(aux, (hipEvent_t)c->ev_fork, 0));
         // from here on the second queue holds work: whatever fails below, it is joined back into the caller's stream before the
         // call returns (both queues touch the context's tables and d_binary)
-        if (stag) {
-            rc = lm_label_launch(c, src, n0, n_frames - n0, d_labels, aux, 0);
-            if (rc == LM_OK) rc = lm_label_launch(c, src, 0, n0, d_labels, st, 2);
-        } else {
-            for (int k = 0, f0 = 0; k < parts && rc == LM_OK; k++) {
-                const int n = n_frames / parts + (k < n_frames % parts ? 1 : 0);
-                rc = lm_label_launch(c, src, f0, n, d_labels, (k & 1) ? aux : st);
-                f0 += n;
-            }
+        int rc = LM_OK;
+        for (int k = 0, f0 = 0; k < parts && rc == LM_OK; k++) {
+            const int n = n_frames / parts + (k < n_frames % parts ? 1 : 0);
+            rc = lm_label_launch(c, src, f0, n, d_labels, (k & 1) ? aux : st);
+            f0 += n;
         }
         const hipError_t e1 = hipEventRecord((hipEvent_t)c->ev_join, aux);
         const hipError_t e2 = (e1 == hipSuccess) ? hipStreamWaitEvent(st, (hipEvent_t)c->ev_join, 0) : e1;
@@ -613,7 +573,6 @@ extern "C" void lm_stream_destroy(LmStream* s)
             if (p) (void)hipFree(p);
         delete m;
     }
-    if (s->twin_stream) (void)hipStreamDestroy((hipStream_t)s->twin_stream);
     for (int i = 0; i < s->n_run_events; i++) (void)hipEventDestroy(s->run_events[i]);
     free(s->run_events);
     if (s->rd_scratch) (void)hipFree(s->rd_scratch);
@@ -758,15 +717,9 @@ static void lm_flush_tempo(LmStream* s, hipStream_t st)
     s->tempo_B = 0;
 }
 
-// st_twin / ev_twin / ev_nt (lm_stream_run_logits, batches of one chunk): the twin-detection kernels of the batch go to st_twin -- the caller has
-// made that queue wait for the batch's records -- and `st` picks up behind them (ev_twin); ev_nt is recorded on `st` behind lm_k_mb_nt, the last
-// reader of the per-batch non-twin counters the NEXT batch's twin kernels reset (the caller makes st_twin wait for it).  Twin detection needs a
-// batch's records only, so it runs while `st` is still replaying the batch before: ~56 us per batch off the matching queue's chain.
-static void lm_launch_match_frames(LmStream* s, int f0, int n, hipStream_t st, hipEvent_t ev_pre = nullptr, bool defer_tempo = false,
-                                   hipStream_t st_twin = nullptr, hipEvent_t ev_twin = nullptr, hipEvent_t ev_nt = nullptr)
+static void lm_launch_match_frames(LmStream* s, int f0, int n, hipStream_t st, hipEvent_t ev_pre = nullptr, bool defer_tempo = false)
 {
     if (!s->match_per_frame) lm_flush_tempo(s, st);
-    if (n > LM_MB_MAX_FRAMES) st_twin = nullptr;
     if (s->match_per_frame) {
         for (int i = 0; i < n; i++) lm_launch_match(s, f0 + i, st);
         return;
@@ -780,16 +733,13 @@ static void lm_launch_match_frames(LmStream* s, int f0, int n, hipStream_t st, h
         const int twins = (s->min_recall <= 1.0 && s->min_precision <= 1.0) ? 1 : 0;     // the twin rule needs "identical crops are accepted"; otherwise twin[] stays 0
         if (twins) {
             const dim3 gc(LM_HIP_EMULATED ? 2 : 256);
-            const hipStream_t tq = st_twin ? st_twin : st;
-            hipLaunchKernelGGL(lm_k_mb_twin_insert, gc, dim3(256), 0, tq, s->cc, s->chash, s->frame_cc_off, f, B, s->counters, mb);
-            hipLaunchKernelGGL(lm_k_mb_twin_probe, gc, dim3(256), 0, tq, s->cc, s->frame_cc_off, f, B, s->counters, mb, s->max_gap);
-            hipLaunchKernelGGL(lm_k_mb_twin_cmp, ge, dim3(256), 0, tq, s->cc, s->crop, s->frame_cc_off, f, B, s->counters, mb);
-            hipLaunchKernelGGL(lm_k_mb_twin_final, gc, dim3(256), 0, tq, s->cc, s->frame_cc_off, f, B, s->counters, mb);
-            if (st_twin) { (void)hipEventRecord(ev_twin, st_twin); (void)hipStreamWaitEvent(st, ev_twin, 0); }
+            hipLaunchKernelGGL(lm_k_mb_twin_insert, gc, dim3(256), 0, st, s->cc, s->chash, s->frame_cc_off, f, B, s->counters, mb);
+            hipLaunchKernelGGL(lm_k_mb_twin_probe, gc, dim3(256), 0, st, s->cc, s->frame_cc_off, f, B, s->counters, mb, s->max_gap);
+            hipLaunchKernelGGL(lm_k_mb_twin_cmp, ge, dim3(256), 0, st, s->cc, s->crop, s->frame_cc_off, f, B, s->counters, mb);
+            hipLaunchKernelGGL(lm_k_mb_twin_final, gc, dim3(256), 0, st, s->cc, s->frame_cc_off, f, B, s->counters, mb);
         }
         hipLaunchKernelGGL(lm_k_mb_nt, dim3(B + 1), dim3(1024), 0, st, s->frame_cc_off, f, B, s->active, s->active_cc, s->active_box, s->active_last,
                            s->counters, mb, s->max_gap, twins);
-        if (twins && st_twin) (void)hipEventRecord(ev_nt, st);
         hipLaunchKernelGGL((lm_k_mb_join<0, 0>), gj, dim3(256), 0, st, s->cc, s->frame_cc_off, f, B, s->active_box, s->active_cc, s->counters, mb);
         hipLaunchKernelGGL((lm_k_mb_join<0, 1>), gj, dim3(256), 0, st, s->cc, s->frame_cc_off, f, B, s->active_box, s->active_cc, s->counters, mb);
         hipLaunchKernelGGL((lm_k_mb_eval<0>), ge, dim3(256), 0, st, s->cc, s->crop, s->frame_cc_off, f, B, s->active_last, s->counters, mb,
@@ -928,29 +878,12 @@ extern "C" int lm_stream_run_logits(LmStream* s, const float* d_logits, int n_fr
     const bool gated = two && schedule == 1 && batch <= LM_MB_MAX_FRAMES && !s->match_per_frame;
     const size_t px = (size_t)s->ctx->g.W * s->ctx->g.H;
     const int nb = (n_frames + batch - 1) / batch;
-    if (two) { const int rc = lm_run_events(s, 3 * nb + 2 * nb); if (rc) return rc; }
-    // events of batch k: 3k = labelled, 3k + 1 = records appended, 3k + 2 = its matching has reached the replay kernel;
-    // behind those, 3 nb + 2k = its twin detection is done, 3 nb + 2k + 1 = its lm_k_mb_nt is done
+    if (two) { const int rc = lm_run_events(s, 3 * nb); if (rc) return rc; }
+    // events of batch k: 3k = labelled, 3k + 1 = records appended, 3k + 2 = its matching has reached the replay kernel
     hipEvent_t* ev = s->run_events;
-    hipEvent_t* ev2 = s->run_events + 3 * nb;
-    // LM_TWIN_QUEUE=1 (free schedule): twin detection of batch k on a queue of its own, beside the replay of batch k - 1.  Measured
-    // (profiles/r03_s2_operating_points.txt): 62-63 k frames/s against 68-70 k without -- one more queue of wide kernels beside the labelling
-    // launches costs more than the ~56 us per batch it takes off the matching queue's chain.  Off by default.
-    static const int twin_queue = [] { const char* e = getenv("LM_TWIN_QUEUE"); return e ? atoi(e) : 0; }();
-    hipStream_t st_twin = nullptr;
-    if (two && twin_queue && !s->match_per_frame && batch <= LM_MB_MAX_FRAMES) {
-        if (!s->twin_stream) LM_HIP(hipStreamCreateWithFlags((hipStream_t*)&s->twin_stream, hipStreamNonBlocking));
-        st_twin = (hipStream_t)s->twin_stream;
-    }
     int prev_n = 0;
-    // LM_RUN_AHEAD=R (two-stream forms): the launch loop stays at most R batches ahead of the GPU (it waits for the records of batch
-    // k - R before it enqueues batch k).  A stream's ~4,500 launches enqueued at once fill the hardware queues for >100 ms; kernels
-    // that another host thread submits meanwhile (step 03 of the previous stream) on a stream that shares a hardware queue with this
-    // one's wait behind all of them.  0 (default) = no limit.
-    static const int run_ahead = [] { const char* e = getenv("LM_RUN_AHEAD"); return (e && atoi(e) > 0) ? atoi(e) : 0; }();
     for (int k = 0, f0 = 0; f0 < n_frames; f0 += batch, k++) {
         const int n = (n_frames - f0 < batch) ? n_frames - f0 : batch;
-        if (two && run_ahead > 0 && k >= run_ahead) LM_HIP(hipEventSynchronize(ev[3 * (k - run_ahead) + 1]));
         if (gated && k >= 2) LM_HIP(hipStreamWaitEvent(sw, ev[3 * (k - 2) + 2], 0));       // the wide kernels of matching k-2 are through
         int rc = lm_label_batch_logits(s->ctx, d_logits + (size_t)f0 * px, n, thr, 1, d_binary, d_labels, stream_wide);
         if (rc) return rc;
@@ -964,15 +897,8 @@ extern "C" int lm_stream_run_logits(LmStream* s, const float* d_logits, int n_fr
         } else if (!gated) {
             LM_HIP(hipEventRecord(ev[3 * k + 1], sw));
             LM_HIP(hipStreamWaitEvent(sm, ev[3 * k + 1], 0));
-            if (st_twin) {
-                LM_HIP(hipStreamWaitEvent(st_twin, ev[3 * k + 1], 0));
-                if (k >= 1) LM_HIP(hipStreamWaitEvent(st_twin, ev2[2 * (k - 1) + 1], 0));
-                lm_launch_match_frames(s, s->frames_matched, n, sm, nullptr, false, st_twin, ev2[2 * k], ev2[2 * k + 1]);
-                s->frames_matched += n;
-            } else {
-                rc = lm_stream_match(s, n, stream_match);
-                if (rc) return rc;
-            }
+            rc = lm_stream_match(s, n, stream_match);
+            if (rc) return rc;
         } else {
             LM_HIP(hipEventRecord(ev[3 * k + 1], sw));
             if (k >= 1) {               // matching of batch k-1 starts when batch k has been labelled (which implies its records are in)

@@ -675,53 +675,6 @@ __global__ void __launch_bounds__(256) lm_k_apply_labels(const int32_t* __restri
 }
 
 // ------------------------------------------------------------------------------------------------
-// K4b + K5a + K5b as ONE launch ("per-frame pipelined middle"): a workgroup per (band, frame) runs its seam unions, waits
-// until the frame's other bands have done theirs, flattens and flags its band, waits again (the numbering needs every band's root
-// count and root flags), and numbers its runs.  The two waits are per-FRAME arrival counters in HBM -- three grid-wide kernel
-// boundaries become two 34-workgroup rendezvous that other frames' workgroups compute under.  Hand-off per MI355X_MICROARCH.md
-// ("Valid forms"): every wave's stores drained + workgroup barrier (__syncthreads), lane 0: agent-scope release, drain, relaxed
-// agent-scope arrival; then one relaxed poll loop, one agent-scope acquire, drain, workgroup barrier, plain loads.
-// Workgroups take (frame, band) from a ticket counter in arrival order, so a waiting workgroup only ever waits for workgroups that
-// have started -- no assumption on dispatch order or residency.  Counters are never reset: the host passes the launch's base
-// values (cumulative tickets / arrivals of the earlier launches on the same counter set).  GPU builds only: the CPU emulator runs
-// workgroups one after another and keeps the three launches.
-// ------------------------------------------------------------------------------------------------
-#if !LM_HIP_EMULATED
-LM_DEV void lm_frame_rendezvous(unsigned* counter, unsigned target)
-{
-    __syncthreads();                    // every wave: its stores are drained (s_waitcnt vmcnt(0)) and it has reached this point
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        while ((int)(__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) < 0) __builtin_amdgcn_s_sleep(8);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-}
-
-__global__ void __launch_bounds__(256) lm_k_middle(const uint64_t* __restrict__ bits, const uint64_t* __restrict__ starts, const uint16_t* __restrict__ prefix,
-                                                   const uint32_t* __restrict__ rowoff, const uint8_t* __restrict__ band_fallback, int32_t* parent,
-                                                   const int32_t* __restrict__ band_runs, unsigned long long* rootbits, uint32_t* wordprefix,
-                                                   uint32_t* band_roots, uint32_t* __restrict__ band_base, int32_t* __restrict__ n_labels,
-                                                   int32_t* __restrict__ final_label, int WW, int H, int cap, int brows, int slot, int capw, int nbands,
-                                                   unsigned* __restrict__ sync, unsigned ticket_base, unsigned arrive_base, const LmStatInit si)
-{
-    // sync[0]: tickets; sync[1 + 2 * frame + phase]: arrivals of the frame's workgroups at rendezvous `phase`
-    __shared__ unsigned s_ticket;
-    if (threadIdx.x == 0) s_ticket = __hip_atomic_fetch_add(sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - ticket_base;
-    __syncthreads();
-    const int b = (int)(s_ticket / (unsigned)nbands), band = (int)(s_ticket - (unsigned)b * nbands);
-    lm_seam_body(b, band, nbands, bits, starts, prefix, rowoff, band_fallback, parent, WW, H, cap, brows);
-    lm_frame_rendezvous(sync + 1 + 2 * b, arrive_base + (unsigned)nbands);
-    lm_flatten_body(b, band, nbands, parent, band_runs, rootbits, wordprefix, band_roots, slot, cap, capw);
-    lm_frame_rendezvous(sync + 2 + 2 * b, arrive_base + (unsigned)nbands);
-    lm_apply_body(b, band, nbands, parent, band_runs, rootbits, wordprefix, band_roots, band_base, n_labels, final_label, slot, cap, capw, si);
-}
-#endif
-
-// ------------------------------------------------------------------------------------------------
 // K6: write the int32 label image (4 B/px, the only HBM write of the labelling).  One thread handles LM_WL_Q quads
 // of 4 pixels, quad = base + k*64 + lane, so every store instruction of a wave covers a contiguous 1 KiB while the
 // (dependent) run-table lookups of the LM_WL_Q quads are independent of each other and issued phase by phase.

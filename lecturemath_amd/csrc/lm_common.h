@@ -13,7 +13,8 @@
 // A "run" is a maximal horizontal segment of foreground pixels; runs are numbered in raster order,
 // so the smallest run id of a component starts at the component's first pixel in raster order and
 // numbering roots in id order reproduces scipy.ndimage.label's numbering (labeler.py:126).
-// CAP = nbands * SLOT with SLOT = 64 * ceil(W/2) (worst-case runs of a 64-row band), so there is no overflow path.
+// CAP = nbands * SLOT with SLOT = band_rows * ceil(W/2) rounded up to a multiple of 64 (worst-case runs of a band), so there is no
+// overflow path.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -63,7 +64,6 @@ struct LmCtx {
     uint32_t* band_base;     // [B][nbands] labels (roots) in the bands above
     uint32_t* band_roots;    // [B][nbands] roots per band
     uint8_t* band_fallback;  // [B][nbands] 1 = forest too large for LDS, unions done in L2
-    unsigned* mid_sync;      // [2 queues][1 + 2 * B] ticket + per-frame arrival counters of lm_k_middle
     int nbands, slot;        // bands of band_rows rows; slot = id space per band (worst-case runs, multiple of 64)
     int band_rows;           // 32 up to 2048 px wide, 16 above (lm_cc_kernels.hip)
     int32_t* parent;         // [B][cap]
@@ -99,7 +99,6 @@ struct LmCtx {
     void* ev_join;
 };
 
-#define LM_LABEL_FUSED_MIDDLE_DEFAULT 0     // 1: lm_k_middle (one launch, per-frame rendezvous) instead of seam / flatten / apply launches; env LM_LABEL_FUSED_MIDDLE overrides
 // parts a batch is labelled in, side by side on two queues (env LM_LABEL_PARTS overrides: 1..8).  Two parts shorten the launch
 // sequence where it shares the GPU with other work (0.39 of the HBM peak in the pipeline's timed region instead of 0.30-0.32) by
 // filling the gaps of its latency-bound middle with the other half of the batch -- but that is where the OTHER kernels of the

@@ -130,7 +130,6 @@ class FcnEngine:
     # {layer: channel tiles per workgroup} where fcn2.pick_mt's rule is not the fastest (profiles/r04_mt_{default,a,b}.txt: conv_down_1 on ONE
     # tile = 24,480 small workgroups at 114 VGPRs, 139 -> 124-130 us -- it is a 250 MB store; every other layer is fastest on pick_mt's choice)
     DEFAULT_MT = {L_DOWN: 1}
-    DEFAULT_LDS = {}        # {layer: LDS bytes a workgroup may take}; default 80 KB = two workgroups per CU
     DEFAULT_VARIANTS = {L_UPC + 4: (2, 0), L_TEXT: (2, 0), L_PX1: (2, 0), L_PX2: (2, 0), L_MID: (1, 1), L_UPC: (1, 1)}
 
     def __init__(self, widths, pixel_kernel, kernel, max_h, max_w, lib=None, precision="mixed", formats=None):
@@ -148,10 +147,6 @@ class FcnEngine:
         self.formats = dict(formats or {})
         # planar engine only: {layer id: (column tiles per wave 1 | 2, loader wave 0 | 1)} -- the kernel variant of a layer (lm_k_g2's NC, LOADER)
         self.variants = dict(self.DEFAULT_VARIANTS)
-        if os.environ.get("LM_FCN_VARIANTS"):                           # experiments: "18=2:0,5=1:1"
-            for kv in os.environ["LM_FCN_VARIANTS"].split(","):
-                k, v = kv.split("=")
-                self.variants[int(k)] = tuple(int(x) for x in v.split(":"))
         self.lib = lib or _lib.load()
         self.be = Backend(self.lib)
         self.widths = [int(v) for v in widths]
@@ -220,41 +215,22 @@ class FcnEngine:
         def V(layer):
             nc, loader = self.variants.get(layer, (1, 0))
             return {"nc": nc, "loader": loader}
-        lds_over = {}
-        if os.environ.get("LM_FCN2_LDS"):                                  # experiments: "18=53000,15=53000" (bytes of LDS a workgroup may take)
-            lds_over = {int(k): int(v) for k, v in (kv.split("=") for kv in os.environ["LM_FCN2_LDS"].split(","))}
-        lds_over = {**self.DEFAULT_LDS, **lds_over}
-
-        def LDS(layer, default=f2.LDS_TWO_WORKGROUPS):
-            return lds_over.get(layer, default)
-        mt_over = {}
-        if os.environ.get("LM_FCN2_MT"):                                   # experiments: channel tiles per workgroup, "0=1,10=2"
-            mt_over = {int(k): int(v) for k, v in (kv.split("=") for kv in os.environ["LM_FCN2_MT"].split(","))}
-        mt_over = {**self.DEFAULT_MT, **mt_over}
-        gs_over = {}
-        if os.environ.get("LM_FCN2_GSIZE"):                                # experiments: slices per weight group, "18=2,15=3"
-            gs_over = {int(k): int(v) for k, v in (kv.split("=") for kv in os.environ["LM_FCN2_GSIZE"].split(","))}
+        MT = self.DEFAULT_MT.get
         recipes = {}
-        # feature octets per chunk of conv_pixels_2: one, so that the 16 x 32 tile's patch planes of the split format leave room for two
-        # workgroups per CU (two octets: 88 KB of LDS, one workgroup, 757 us; one octet: 76 KB, 338 us; 16 x 16 tiles: 364 us)
-        px_octets = int(os.environ.get("LM_FCN2_PX_OCTETS", "1" if self.variants.get(L_PX2, (1, 0))[0] == 2 else "2"))
-        deep_lds = int(os.environ.get("LM_FCN2_DEEP_LDS", str(f2.LDS_TWO_WORKGROUPS)))    # experiments: LDS of the layers with <= ~1 workgroup per CU
-
-        def lds_for(layer_tiles, cout, mt_guess=4):
-            return deep_lds if layer_tiles * max(1, cout // (16 * mt_guess)) <= 320 else f2.LDS_TWO_WORKGROUPS
+        # every layer aims at fcn2.LDS_TWO_WORKGROUPS of LDS (build's and conv_layer's default): two workgroups per CU
         # encoder: layer 1 reads the input pair plane (3 channels, two horizontal taps per slot)
         w, b = conv_bn("conv_down_block_1")
         pairs = [f2.pairplane_pair(0, dy, dx, 0, 3) for dy in range(3) for dx in (0, 2)]
-        recipes[L_DOWN] = (f2.build([w], [{"planes": [(f2.T_X0P, 0)], "pairs": pairs}], 3, 3, T(L_DOWN), mt_over.get(L_DOWN) or f2.pick_mt(d1, tiles(0) // V(L_DOWN)["nc"]), f2.EPI_PO, lds_target=LDS(L_DOWN), **V(L_DOWN)), b)
+        recipes[L_DOWN] = (f2.build([w], [{"planes": [(f2.T_X0P, 0)], "pairs": pairs}], 3, 3, T(L_DOWN), MT(L_DOWN) or f2.pick_mt(d1, tiles(0) // V(L_DOWN)["nc"]), f2.EPI_PO, **V(L_DOWN)), b)
         cin = [3] + downs
         for n in range(1, 5):
             w, b = conv_bn("conv_down_block_%d" % (n + 1))
-            recipes[L_DOWN + n] = (f2.conv_layer(w, [(f2.T_POOL0 + n - 1, cin[n] // 8)], T(L_DOWN + n), tiles(n), mt=mt_over.get(L_DOWN + n), lds_target=LDS(L_DOWN + n, lds_for(tiles(n), downs[n])), **V(L_DOWN + n)), b)
+            recipes[L_DOWN + n] = (f2.conv_layer(w, [(f2.T_POOL0 + n - 1, cin[n] // 8)], T(L_DOWN + n), tiles(n), mt=MT(L_DOWN + n), **V(L_DOWN + n)), b)
         w, b = conv_bn("mid_block")
-        recipes[L_MID] = (f2.conv_layer(w, [(f2.T_POOL0 + 4, d5 // 8)], T(L_MID), tiles(5), mt=mt_over.get(L_MID), lds_target=LDS(L_MID, lds_for(tiles(5), mid, 2)), **V(L_MID)), b)
+        recipes[L_MID] = (f2.conv_layer(w, [(f2.T_POOL0 + 4, d5 // 8)], T(L_MID), tiles(5), mt=MT(L_MID), **V(L_MID)), b)
         ups = {5: (mid, u5, c5, d5), 4: (c5, u4, c4, d4), 3: (c4, u3, c3, d3), 2: (c3, u2, c2, d2), 1: (c2, u1, c1, d1)}
         for i, lvl in enumerate((5, 4, 3, 2, 1)):
-            tin, u, c, skip = ups[lvl]
+            tin, u, _, skip = ups[lvl]
             wt = _np(sd["transposed_conv_%d.weight" % lvl]).astype(np.float32)          # [Cin][Cout][2][2]
             bt = _np(sd["transposed_conv_%d.bias" % lvl]).astype(np.float32)
             wt, bt = fold_bn(wt, bt, sd, "upsample_block_%d.0" % lvl, 1)
@@ -262,7 +238,7 @@ class FcnEngine:
             n8 = tin // 8
             co = 8 if n8 % 8 == 0 else (4 if n8 % 4 == 0 else 2)
             chunks = f2.conv_chunks([(src, n8)], 1, 1, co)
-            if u % 32 == 0 and not mt_over.get(L_UPT + i):
+            if u % 32 == 0 and not MT(L_UPT + i):
                 # both dx of a 32-channel block in one workgroup: per dy a virtual output axis [block][dx][32 channels]
                 w2 = []
                 for dy in (0, 1):
@@ -271,9 +247,9 @@ class FcnEngine:
                 recipes[L_UPT + i] = (f2.build(w2, chunks, 1, 1, T(L_UPT + i), 4, f2.EPI_TC2), bt)
             else:
                 w4 = [np.ascontiguousarray(wt[:, :, dy, dx].T)[:, :, None, None] for dy in (0, 1) for dx in (0, 1)]
-                recipes[L_UPT + i] = (f2.build(w4, chunks, 1, 1, T(L_UPT + i), mt_over.get(L_UPT + i) or f2.pick_mt(u, tiles(lvl)), f2.EPI_TC), bt)
+                recipes[L_UPT + i] = (f2.build(w4, chunks, 1, 1, T(L_UPT + i), MT(L_UPT + i) or f2.pick_mt(u, tiles(lvl)), f2.EPI_TC), bt)
             w, b = conv_bn("conv_up_block_%d" % lvl)                                      # input = cat(up, skip_pre)
-            recipes[L_UPC + i] = (f2.conv_layer(w, [(f2.T_UPT0 + i, u // 8), (f2.T_PRE0 + lvl - 1, skip // 8)], T(L_UPC + i), tiles(lvl - 1), mt=mt_over.get(L_UPC + i), gsize=gs_over.get(L_UPC + i), lds_target=LDS(L_UPC + i, lds_for(tiles(lvl - 1), c, 2 if i == 0 else 4)), **V(L_UPC + i)), b)
+            recipes[L_UPC + i] = (f2.conv_layer(w, [(f2.T_UPT0 + i, u // 8), (f2.T_PRE0 + lvl - 1, skip // 8)], T(L_UPC + i), tiles(lvl - 1), mt=MT(L_UPC + i), **V(L_UPC + i)), b)
         # heads: the text + reconstruction row convolution is fused with its vertical sums (EPI_V; 56 + 77 -> 93 us: the 133 MB fp32 row buffer
         # is neither written nor read back); the output logit's is not (62 + 20 -> 87 us fused: its tiles of 10 finished rows cost more
         # row-convolution work than its 66 MB of rows; profiles/r04_heads_*.txt).  LM_FCN2_FUSED_HEADS: bit 0 = text / rec, bit 1 = output.
@@ -282,16 +258,17 @@ class FcnEngine:
         wt, bt = conv_bn("conv_text_mask_out")
         wr, br = conv_bn("conv_reconstruct")
         rows = f2.text_rec_rows(wt, wr)
-        recipes[L_TEXT] = (f2.build([rows], f2.conv_chunks([(f2.T_XUP, c1 // 8)], 1, 7, c1 // 8), 1, 7, T(L_TEXT), 1, head_epi, lds_target=LDS(L_TEXT), **V(L_TEXT)),
+        recipes[L_TEXT] = (f2.build([rows], f2.conv_chunks([(f2.T_XUP, c1 // 8)], 1, 7, c1 // 8), 1, 7, T(L_TEXT), 1, head_epi, **V(L_TEXT)),
                            np.concatenate([np.zeros(16, np.float32), bt, br]))
+        # the pixel branch: patch planes single-buffered; feature octets per chunk: two in conv_pixels_1, one in conv_pixels_2, so that
+        # the 16 x 32 tile's patch planes of the split format leave room for two workgroups per CU (two octets: 88 KB of LDS, one
+        # workgroup, 757 us; one octet: 76 KB, 338 us; 16 x 16 tiles: 364 us)
         w, b = conv_bn("conv_pixels_1")
-        px1_octets = int(os.environ.get("LM_FCN2_PX1_OCTETS", "2"))                     # experiments: feature octets per chunk of conv_pixels_1
-        px_pdouble = [bool(int(v)) for v in os.environ.get("LM_FCN2_PX_PDOUBLE", "0,0").split(",")]      # ... double-buffered patch planes (px1, px2)
-        recipes[L_PX1] = (f2.build([w], f2.pixel_chunks(f2.T_XUP, c1 // 8, f2.T_DP, 7, 7, octets=px1_octets), 7, 7, T(L_PX1), 2 if pm1 % 32 == 0 else 1, f2.EPI_PO, pdouble=px_pdouble[0], gsize=gs_over.get(L_PX1), lds_target=LDS(L_PX1), **V(L_PX1)), b)
+        recipes[L_PX1] = (f2.build([w], f2.pixel_chunks(f2.T_XUP, c1 // 8, f2.T_DP, 7, 7, octets=2), 7, 7, T(L_PX1), 2 if pm1 % 32 == 0 else 1, f2.EPI_PO, pdouble=False, **V(L_PX1)), b)
         w, b = conv_bn("conv_pixels_2")
-        recipes[L_PX2] = (f2.build([w], f2.pixel_chunks(f2.T_P1, pm1 // 8, f2.T_DP, 7, 7, octets=px_octets), 7, 7, T(L_PX2), 2 if pm2 % 32 == 0 else 1, f2.EPI_PO, pdouble=px_pdouble[1], gsize=gs_over.get(L_PX2), lds_target=LDS(L_PX2), **V(L_PX2)), b)
+        recipes[L_PX2] = (f2.build([w], f2.pixel_chunks(f2.T_P1, pm1 // 8, f2.T_DP, 7, 7, octets=1), 7, 7, T(L_PX2), 2 if pm2 % 32 == 0 else 1, f2.EPI_PO, pdouble=False, **V(L_PX2)), b)
         w, b = conv_bn("conv_out")
-        recipes[L_OUT] = (f2.build([f2.out_rows(w)], f2.pixel_chunks(f2.T_P2, pm2 // 8, f2.T_DP, 1, 7), 1, 7, T(L_OUT), 1, out_epi, pdouble=False, lds_target=LDS(L_OUT), **V(L_OUT)),
+        recipes[L_OUT] = (f2.build([f2.out_rows(w)], f2.pixel_chunks(f2.T_P2, pm2 // 8, f2.T_DP, 1, 7), 1, 7, T(L_OUT), 1, out_epi, pdouble=False, **V(L_OUT)),
                           np.concatenate([np.zeros(16, np.float32), b]))
         # a tensor keeps its lo parts when a layer reading it runs the split format
         lo = np.zeros(f2.N_TENSORS, np.int32)

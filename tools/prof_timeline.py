@@ -8,7 +8,7 @@ rows = db.execute("select name,start,end,stream_id from kernels order by start")
 def cls(n):
     n = n.split("(")[0]
     if "rocclr" in n: return "blit"
-    if any(k in n for k in ("pack_rows", "lm_k_band", "seam_union", "flatten_flag", "apply_labels", "write_labels", "lm_k_middle")): return "label"
+    if any(k in n for k in ("pack_rows", "lm_k_band", "seam_union", "flatten_flag", "apply_labels", "write_labels")): return "label"
     if any(k in n for k in ("lm_k_stats", "lm_k_select", "batch_offsets", "lm_k_emit")): return "records"
     if "lm_k_mb_resolve" in n or "lm_k_mb_sources" in n: return "replay"
     if "lm_k_mb_" in n: return "match"
