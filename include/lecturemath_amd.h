@@ -294,6 +294,18 @@ int lm_fcn2_set_layer(LmFcn2* f, int layer, const int32_t* desc, int ndesc, cons
                       const float* h_bias, int nbias);
 /* same contract as lm_fcn_forward */
 int lm_fcn2_forward(LmFcn2* f, const uint8_t* d_rgb, int h, int w, float* d_out, float* d_text, float* d_rec, void* stream);
+/* Power-of-two range scales, all zero after lm_fcn2_create (every result is then bit for bit what it is without them).
+ * tensor_exp25[t] = e: the epilogue producing activation tensor t stores x * 2^-e (hi, lo and the pooled copy); the caller multiplies every
+ * consumer's weights for those input channels by 2^e before packing them.  layer_wexp21[l] = k: the caller packs layer l's weights as
+ * w * 2^-k and the layer computes fma(acc, 2^k, bias) -- every layer accepts one, the head rows included (acc * 2^k before their vertical
+ * sums).  Exact short of fp32 overflow; exponents in [-100, 100].  The network input (tensor 0) and the diff (22) keep exponent 0; pooled
+ * tensor 6 + n carries the exponent of tensor 1 + n.  Either pointer may be null (left as it is).  HOST pointers. */
+int lm_fcn2_set_scales(LmFcn2* f, const int32_t* tensor_exp25, const int32_t* layer_wexp21);
+/* Range statistics of the activation arena as the last lm_fcn2_forward left it: h_stats[28][5] doubles (HOST), rows 0..24 the tensors
+ * (hi planes), 25..27 the fp32 images d_out / d_text / d_rec of that forward (device pointers, 16-byte aligned, each may be null: row
+ * of zeros).  Columns: max |x| as stored (infinity: the tensor overflowed; NaN: it holds one), non-finite values, non-zero values
+ * with a subnormal bit pattern, zeros, values examined.  Only the interior of the last frame's geometry is read.  Synchronises `stream`. */
+int lm_fcn2_range_stats(LmFcn2* f, const float* d_out, const float* d_text, const float* d_rec, double* h_stats, void* stream);
 
 /* ====================================================================================================
  * PNG hand-off codec (csrc/lm_png.hip): 8-bit grayscale, non-interlaced PNG files of width x height frames, encoded and

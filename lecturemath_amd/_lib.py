@@ -92,6 +92,8 @@ SIGNATURES = {
     "lm_fcn2_destroy": (None, [_vp]),
     "lm_fcn2_set_layer": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _i64, ctypes.c_int, _vp, ctypes.c_int]),
     "lm_fcn2_forward": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "lm_fcn2_set_scales": (ctypes.c_int, [_vp, _vp, _vp]),
+    "lm_fcn2_range_stats": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "lm_png_create": (_vp, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "lm_png_destroy": (None, [_vp]),
     "lm_png_encode_bound": (_i64, [ctypes.c_int, ctypes.c_int]),

@@ -142,6 +142,9 @@ struct LmG2Args {
     int act;                        // LM_ACT_GELU or LM_ACT_NONE
     int tc_merged;                  // EPI_TC: 1 = LM_G2_EPI_TC2 (parity = dy, tile pair q = dx)
     int stamp;                      // diagnostic builds: this launch writes its stamps
+    // power-of-two range scales (lm_fcn2_set_scales; both 1.0f by default, which leaves every result bit for bit as without them):
+    float wscale;                   // 2^k: the host packed this layer's weights as w * 2^-k, the epilogues compute fma(acc, 2^k, bias)
+    float oscale;                   // 2^-e: the planar epilogues store act(..) * 2^-e; the consumers' weights carry the 2^e
     // EPI_PO / EPI_TC output tensor
     char* out_hi; char* out_lo;     // plane 0 of the hi / lo parts (lo may be null)
     long long out_plane;            // bytes per plane
@@ -427,7 +430,7 @@ __global__ void __launch_bounds__(LOADER ? 320 : 256, LOADER ? (((TERMS != 1 && 
 #pragma unroll
             for (int n = 0; n < 4; n++) {
                 const lm_f32x4 v = acc[0][c * 4 + n];
-                *(float4*)(s_T + (((wave * 4 + n) * TW + c * 16 + col) * 16 + 4 * kg)) = make_float4(v[0], v[1], v[2], v[3]);
+                *(float4*)(s_T + (((wave * 4 + n) * TW + c * 16 + col) * 16 + 4 * kg)) = make_float4(v[0] * a.wscale, v[1] * a.wscale, v[2] * a.wscale, v[3] * a.wscale);
             }
         lm_lds_barrier();
         const int yb = ty * LM_G2_V_ROWS, xb = tx * TW;
@@ -483,7 +486,7 @@ __global__ void __launch_bounds__(LOADER ? 320 : 256, LOADER ? (((TERMS != 1 && 
             for (int n = 0; n < 4; n++) {
                 const int y = y0 + n;
                 const lm_f32x4 v = acc[0][c * 4 + n];
-                if (y < a.H) LM_G2_STORE(float4, a.tout + ((long long)y * a.W + x) * a.ts + 4 * kg, make_float4(v[0], v[1], v[2], v[3]));
+                if (y < a.H) LM_G2_STORE(float4, a.tout + ((long long)y * a.W + x) * a.ts + 4 * kg, make_float4(v[0] * a.wscale, v[1] * a.wscale, v[2] * a.wscale, v[3] * a.wscale));
             }
         }
     } else {
@@ -499,6 +502,8 @@ __global__ void __launch_bounds__(LOADER ? 320 : 256, LOADER ? (((TERMS != 1 && 
         const long long lo_delta = has_lo ? (long long)(a.out_lo - a.out_hi) : 0;
         const long long rstride = (long long)sc * a.Wp_out * 16;             // bytes between the wave's output rows
         const bool xin = x < a.W;
+        // range scales: fma(acc, 2^k, bias) is acc + bias's single rounding when k = 0, and a product with a power of two is exact
+        const float ws = a.wscale, os = a.oscale;
         // pairs of tiles: the host packs tile 2q with the channels 32q + 8kg + (0..3) in rows 4kg + (0..3) and tile 2q + 1 with
         // 32q + 8kg + 4 + (0..3), so a lane holds one whole octet of its pixel: one 16-byte store per part
 #pragma unroll
@@ -512,7 +517,7 @@ __global__ void __launch_bounds__(LOADER ? 320 : 256, LOADER ? (((TERMS != 1 && 
 #pragma unroll
             for (int n = 0; n < 4; n++)
 #pragma unroll
-                for (int j = 0; j < 8; j++) v[n][j] = lm_gelu_fast(acc[2 * q + (j >> 2)][c * 4 + n][j & 3] + bb[j]);
+                for (int j = 0; j < 8; j++) v[n][j] = lm_gelu_fast(fmaf(acc[2 * q + (j >> 2)][c * 4 + n][j & 3], ws, bb[j])) * os;
 #pragma unroll
             for (int n = 0; n < 4; n++) {
                 if (!xin || y0 + n >= a.H) continue;
@@ -561,7 +566,7 @@ __global__ void __launch_bounds__(LOADER ? 320 : 256, LOADER ? (((TERMS != 1 && 
 #pragma unroll
             for (int n = 0; n < 4; n++)
 #pragma unroll
-                for (int j = 0; j < 4; j++) v[n][j] = lm_gelu_fast(acc[m][c * 4 + n][j] + bb[j]);
+                for (int j = 0; j < 4; j++) v[n][j] = lm_gelu_fast(fmaf(acc[m][c * 4 + n][j], ws, bb[j])) * os;
 #pragma unroll
             for (int n = 0; n < 4; n++) {
                 if (!xin || y0 + n >= a.H) continue;
@@ -695,9 +700,9 @@ __global__ void __launch_bounds__(256) lm_k_vsum2_text_rec(const float* __restri
     }
 }
 
-// rows / columns of a transposed-conv output that no input pixel reaches (output_size = 2 * in + 1): act(bias), planar octets
+// rows / columns of a transposed-conv output that no input pixel reaches (output_size = 2 * in + 1): act(bias) * 2^-e, planar octets
 __global__ void __launch_bounds__(256) lm_k_convT_border2(char* out_hi, char* out_lo, long long plane, int Wp, int halo, int OH, int OW, int H2, int W2,
-                                                          int C8, const float* __restrict__ bias, int act)
+                                                          int C8, const float* __restrict__ bias, int act, float oscale)
 {
     const long long nb_px = (long long)(OH - H2) * OW + (long long)H2 * (OW - W2);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nb_px * C8; i += (long long)gridDim.x * blockDim.x) {
@@ -709,7 +714,7 @@ __global__ void __launch_bounds__(256) lm_k_convT_border2(char* out_hi, char* ou
         lm_h8 hi, lo;
 #pragma unroll
         for (int j = 0; j < 8; j++) {
-            const float v = lm_act(bias[o * 8 + j], act);
+            const float v = lm_act(bias[o * 8 + j], act) * oscale;        // the tensor's 2^-e (lm_fcn2_set_scales)
             hi[j] = (_Float16)v; lo[j] = (_Float16)(v - (float)hi[j]);
         }
         const long long so = (long long)o * plane + ((long long)(y + halo) * Wp + x + halo) * 16;
@@ -722,6 +727,8 @@ __global__ void __launch_bounds__(256) lm_k_convT_border2(char* out_hi, char* ou
 // host side
 // ================================================================================================
 #define LM_F2_TENSORS 25
+#define LM_F2_LAYERS 21                         // layers 0..20 of the forward pass (lm_fcn2_set_scales)
+#define LM_F2_STAT_ROWS (LM_F2_TENSORS + 3)     // lm_fcn2_range_stats: the tensors, then the three fp32 outputs
 enum { LM_F2_X0P = 0, LM_F2_PRE0 = 1, LM_F2_POOL0 = 6, LM_F2_MID = 11, LM_F2_UPT0 = 12, LM_F2_CU0 = 17, LM_F2_XUP = 21, LM_F2_DP = 22, LM_F2_P1 = 23, LM_F2_P2 = 24 };
 
 struct LmF2Tensor {
@@ -750,6 +757,9 @@ struct LmFcn2 {
     LmF2Layer layer[LM_FCN_LAYERS];
     float *tbuf = nullptr, *text = nullptr, *rec4 = nullptr, *outl = nullptr;
     int cur_h = 0, cur_w = 0;
+    int texp[LM_F2_TENSORS] = {0};      // tensor t holds its values * 2^-texp[t] (lm_fcn2_set_scales)
+    int wexp[LM_FCN_LAYERS] = {0};      // layer l's packed weights are w * 2^-wexp[l]
+    unsigned long long* d_stats = nullptr;      // lm_fcn2_range_stats: [LM_F2_STAT_ROWS][4] accumulators
 };
 
 static inline int lm_f2_halo(int level) { return level == 0 ? 3 : 1; }
@@ -769,6 +779,7 @@ extern "C" void lm_fcn2_destroy(LmFcn2* f)
     if (!f) return;
     if (f->arena) (void)hipFree(f->arena);
     for (float* p : {f->tbuf, f->text, f->rec4, f->outl}) if (p) (void)hipFree(p);
+    if (f->d_stats) (void)hipFree(f->d_stats);
     for (auto& l : f->layer)
         for (void* p : {(void*)l.d_w, (void*)l.d_bias, (void*)l.d_groups, (void*)l.d_t4, (void*)l.d_psrc}) if (p) (void)hipFree(p);
     delete f;
@@ -806,13 +817,15 @@ extern "C" LmFcn2* lm_fcn2_create(const int32_t* widths18, const int32_t* lo25, 
     const size_t px = (size_t)max_h * max_w;
     if (hipMalloc((void**)&f->arena, (size_t)off) != hipSuccess || hipMalloc((void**)&f->tbuf, px * 16 * 4) != hipSuccess ||
         hipMalloc((void**)&f->text, px * 4) != hipSuccess || hipMalloc((void**)&f->rec4, px * 16) != hipSuccess ||
-        hipMalloc((void**)&f->outl, px * 4) != hipSuccess) {
+        hipMalloc((void**)&f->outl, px * 4) != hipSuccess || hipMalloc((void**)&f->d_stats, LM_F2_STAT_ROWS * 4 * sizeof(unsigned long long)) != hipSuccess) {
         lm_set_error("lm_fcn2_create: out of device memory (%lld MB of activations)", off >> 20);
         lm_fcn2_destroy(f);
         return nullptr;
     }
     return f;
 }
+
+static int lm_g2_probe(const LmF2Layer& l);
 
 // One layer's recipe (lecturemath_amd/fcn2.py builds it and documents the layout).  desc: kh, kw, terms, mt, epi, nchunks, npc, ngroups,
 // nslices, flags (bits 0-3: column tiles per wave, 1 or 2; bit 8: loader wave; bits 16-23: LDS target in KB), pdouble, wbuf_bytes, cout, then planes [nchunks * npc][2], groups [ngroups][3], slice table [nslices][4].
@@ -843,6 +856,7 @@ extern "C" int lm_fcn2_set_layer(LmFcn2* f, int layer, const int32_t* desc, int 
                          f->t[l.planes[i] < 0 || l.planes[i] >= LM_F2_TENSORS ? 0 : l.planes[i]].c8, f->t[l.planes[i] < 0 || l.planes[i] >= LM_F2_TENSORS ? 0 : l.planes[i]].lo);
             return LM_ERR_ARG;
         }
+    if (int rc = lm_g2_probe(l)) { l = LmF2Layer(); return rc; }     // no kernel instance: refused here, not at the first forward
     l.wblock_bytes = wbytes / wblocks;
     std::vector<int4> groups((size_t)l.ngroups);
     const int nwl = l.terms >= 3 ? 2 : 1;
@@ -901,9 +915,10 @@ template <int KH, int KW, int TERMS, int MT, int EPI, int NC, int LOADER> static
 //   vertical sums (EPI_V): formats 3 / 4, variants 0 and 2
 //   transposed convolutions: formats 1 / 3, 1..4 channel tiles, variant 0
 #define LM_G2_TRY(KH, KW, T, M, E, N, L) \
-    if (l.terms == T && l.mt == M && l.nc == N && l.loader == L) return lm_g2_launch_t<KH, KW, T, M, E, N, L>(a, grid, smem, st);
+    if (l.terms == T && l.mt == M && l.nc == N && l.loader == L) return probe ? LM_OK : lm_g2_launch_t<KH, KW, T, M, E, N, L>(a, grid, smem, st);
 #define LM_G2_TRY_MT4(KH, KW, T, E, N, L) LM_G2_TRY(KH, KW, T, 1, E, N, L) LM_G2_TRY(KH, KW, T, 2, E, N, L) LM_G2_TRY(KH, KW, T, 3, E, N, L) LM_G2_TRY(KH, KW, T, 4, E, N, L)
-static int lm_g2_launch(const LmF2Layer& l, const LmG2Args& a, dim3 grid, size_t smem, hipStream_t st)
+// probe: only answers whether the instance exists (lm_fcn2_set_layer refuses a recipe no kernel can run)
+static int lm_g2_launch(const LmF2Layer& l, const LmG2Args& a, dim3 grid, size_t smem, hipStream_t st, bool probe = false)
 {
     const int shape = l.kh * 10 + l.kw;
     if (l.terms < 1 || l.terms > 4) { lm_set_error("lm_fcn2: operand formats are 1 (f16), 2 (activations split), 3 (both split) or 4 (weights split)"); return LM_ERR_ARG; }
@@ -933,6 +948,152 @@ static int lm_g2_launch(const LmF2Layer& l, const LmG2Args& a, dim3 grid, size_t
 }
 #undef LM_G2_TRY
 #undef LM_G2_TRY_MT4
+static int lm_g2_probe(const LmF2Layer& l)
+{
+    LmG2Args a;
+    memset(&a, 0, sizeof(a));
+    return lm_g2_launch(l, a, dim3(1), 0, nullptr, true);
+}
+
+// Power-of-two range scales (all zero after lm_fcn2_create).  tensor_exp25[t] = e: tensor t is stored as x * 2^-e by its producer's epilogue
+// (hi, lo and the pooled copy alike), and the caller has multiplied every consumer's weights for those input channels by 2^e before packing
+// them.  layer_wexp21[l] = k: the caller packed layer l's weights as w * 2^-k and the epilogue computes fma(acc, 2^k, bias) (the head rows:
+// acc * 2^k before their vertical sums).  Both are exact short of fp32 overflow.  The network input and the diff (pair planes, values in
+// [-2, 2]) keep exponent 0, and a pooled tensor carries the exponent of the tensor it is pooled from.  Either pointer may be null (unchanged).
+extern "C" int lm_fcn2_set_scales(LmFcn2* f, const int32_t* tensor_exp25, const int32_t* layer_wexp21)
+{
+    if (!f) { lm_set_error("lm_fcn2_set_scales: null engine"); return LM_ERR_ARG; }
+    if (tensor_exp25) {
+        for (int t = 0; t < LM_F2_TENSORS; t++)
+            if (tensor_exp25[t] < -100 || tensor_exp25[t] > 100) { lm_set_error("lm_fcn2_set_scales: exponent %d of tensor %d is outside [-100, 100]", tensor_exp25[t], t); return LM_ERR_ARG; }
+        if (tensor_exp25[LM_F2_X0P] || tensor_exp25[LM_F2_DP]) { lm_set_error("lm_fcn2_set_scales: the network input and the diff keep exponent 0"); return LM_ERR_ARG; }
+        for (int n = 0; n < 5; n++)
+            if (tensor_exp25[LM_F2_PRE0 + n] != tensor_exp25[LM_F2_POOL0 + n]) { lm_set_error("lm_fcn2_set_scales: pooled tensor %d must carry the exponent of tensor %d", LM_F2_POOL0 + n, LM_F2_PRE0 + n); return LM_ERR_ARG; }
+    }
+    if (layer_wexp21)
+        for (int l = 0; l < LM_F2_LAYERS; l++)
+            if (layer_wexp21[l] < -100 || layer_wexp21[l] > 100) { lm_set_error("lm_fcn2_set_scales: weight exponent %d of layer %d is outside [-100, 100]", layer_wexp21[l], l); return LM_ERR_ARG; }
+    if (tensor_exp25) memcpy(f->texp, tensor_exp25, sizeof(f->texp));
+    if (layer_wexp21) memcpy(f->wexp, layer_wexp21, LM_F2_LAYERS * sizeof(int));
+    return LM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// range statistics of the activation arena (lm_fcn2_range_stats)
+// ------------------------------------------------------------------------------------------------
+struct LmF2StatRow {
+    const char* base;           // f16 rows: plane 0 of the hi parts; fp32 rows: the image
+    long long plane;            // bytes per plane
+    long long items;            // f16: planes * H * W slots of 16 bytes; fp32: floats
+    int H, W, Wp, halo, f32;
+};
+struct LmF2StatArgs { LmF2StatRow row[LM_F2_STAT_ROWS]; };
+
+// One pass over the INTERIOR of every tensor's hi planes (and the fp32 outputs): per row of `args` the largest |x| as its bit pattern
+// (monotonic for non-negative floats; a NaN sorts above infinity), the number of non-finite values, of non-zero values with a subnormal
+// bit pattern, and of zeros.  16-byte loads, integer tests on the bit patterns, a wave reduction, then one atomic per workgroup for the
+// maximum and one per counter that is not zero (none in a healthy tensor).  acc: [row][4] = max bits, non-finite, subnormal, zero.
+__global__ void __launch_bounds__(256) lm_k_f2_range_stats(const LmF2StatArgs args, unsigned long long* __restrict__ acc)
+{
+    __shared__ unsigned s_red[4][4];
+    const LmF2StatRow r = args.row[blockIdx.y];
+    const long long first = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    if ((long long)blockIdx.x * blockDim.x >= (r.f32 ? (r.items + 3) / 4 : r.items)) return;       // the whole workgroup has nothing to read
+    unsigned mx = 0, nf = 0, sub = 0, zero = 0;
+    if (r.f32) {
+        const long long n4 = r.items / 4;
+        auto one = [&](unsigned u) {
+            u &= 0x7fffffffu;
+            mx = u > mx ? u : mx; nf += u >= 0x7f800000u; sub += (u - 1u) < 0x007fffffu; zero += u == 0;
+        };
+        for (long long i = first; i < n4; i += stride) {
+            const uint4 v = *(const uint4*)(r.base + i * 16);
+            one(v.x); one(v.y); one(v.z); one(v.w);
+        }
+        if (first < r.items - n4 * 4) one(*(const unsigned*)(r.base + (n4 * 4 + first) * 4));
+    } else {
+        const long long hw = (long long)r.H * r.W;
+        for (long long i = first; i < r.items; i += stride) {
+            const long long p = i / hw, q = i - p * hw;
+            const int y = (int)(q / r.W), x = (int)(q - (long long)y * r.W);
+            const uint4 v = *(const uint4*)(r.base + p * r.plane + ((long long)(y + r.halo) * r.Wp + x + r.halo) * 16);
+            const unsigned w4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const unsigned u = (w4[k] >> (16 * h)) & 0x7fffu;
+                    mx = u > mx ? u : mx; nf += u >= 0x7c00u; sub += (u - 1u) < 0x03ffu; zero += u == 0;
+                }
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const unsigned o = __shfl_xor(mx, m);
+        mx = o > mx ? o : mx;
+        nf += __shfl_xor(nf, m); sub += __shfl_xor(sub, m); zero += __shfl_xor(zero, m);
+    }
+    const int wave = (int)(threadIdx.x >> 6);
+    if ((threadIdx.x & 63) == 0) { s_red[wave][0] = mx; s_red[wave][1] = nf; s_red[wave][2] = sub; s_red[wave][3] = zero; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long t[4] = {0, 0, 0, 0};
+        for (int w = 0; w < 4; w++) {
+            t[0] = s_red[w][0] > t[0] ? s_red[w][0] : t[0];
+            for (int k = 1; k < 4; k++) t[k] += s_red[w][k];
+        }
+        unsigned long long* o = acc + (size_t)blockIdx.y * 4;
+        atomicMax(o, t[0]);
+        for (int k = 1; k < 4; k++) if (t[k]) atomicAdd(o + k, t[k]);
+    }
+}
+
+// Range statistics of what the last lm_fcn2_forward left in the arena: h_stats[28][5] doubles = per tensor (0..24) and per fp32 output
+// (25 = d_out, 26 = d_text, 27 = d_rec; a null pointer leaves its row zero): max |x| AS STORED (the hi part, times 2^-e of
+// lm_fcn2_set_scales; infinity when the tensor overflowed, NaN when it holds one), non-finite values, non-zero values whose hi part is
+// subnormal, zeros, values examined.  Only the interior of the last frame's geometry is read: the arena beyond it may hold an older,
+// larger frame.  Pair planes (tensors 0 and 22) hold every pixel twice and two constant zeros per pixel.  One launch; synchronises `stream`.
+extern "C" int lm_fcn2_range_stats(LmFcn2* f, const float* d_out, const float* d_text, const float* d_rec, double* h_stats, void* stream)
+{
+    if (!f || !h_stats) { lm_set_error("lm_fcn2_range_stats: bad arguments"); return LM_ERR_ARG; }
+    if (!f->cur_h || !f->cur_w) { lm_set_error("lm_fcn2_range_stats: no forward pass has run since the layers were set"); return LM_ERR_STATE; }
+    hipStream_t st = (hipStream_t)stream;
+    LmF2StatArgs args;
+    memset(&args, 0, sizeof(args));
+    long long most = 0;
+    for (int i = 0; i < LM_F2_TENSORS; i++) {
+        const LmF2Tensor& t = f->t[i];
+        LmF2StatRow& r = args.row[i];
+        r.base = f->arena + t.off; r.plane = t.plane; r.H = t.H; r.W = t.W; r.Wp = t.Wp; r.halo = t.halo;
+        r.items = (long long)t.c8 * t.H * t.W;
+        most = std::max(most, r.items);
+    }
+    const long long npx = (long long)f->cur_h * f->cur_w;
+    const float* outs[3] = {d_out, d_text, d_rec};
+    for (int i = 0; i < 3; i++) {
+        LmF2StatRow& r = args.row[LM_F2_TENSORS + i];
+        r.f32 = 1; r.base = (const char*)outs[i]; r.items = outs[i] ? npx * (i == 2 ? 3 : 1) : 0;
+        if (((size_t)outs[i]) & 15) { lm_set_error("lm_fcn2_range_stats: output images must be 16-byte aligned"); return LM_ERR_ARG; }
+        most = std::max(most, (r.items + 3) / 4);
+    }
+    LM_HIP(hipMemsetAsync(f->d_stats, 0, LM_F2_STAT_ROWS * 4 * sizeof(unsigned long long), st));
+    const unsigned bx = (unsigned)std::min<long long>((most + 255) / 256, 1024);
+    hipLaunchKernelGGL(lm_k_f2_range_stats, dim3(bx ? bx : 1, LM_F2_STAT_ROWS), dim3(256), 0, st, args, f->d_stats);
+    LM_HIP(hipGetLastError());
+    unsigned long long h[LM_F2_STAT_ROWS * 4];
+    LM_HIP(hipMemcpyAsync(h, f->d_stats, sizeof(h), hipMemcpyDeviceToHost, st));
+    LM_HIP(hipStreamSynchronize(st));
+    for (int i = 0; i < LM_F2_STAT_ROWS; i++) {
+        const LmF2StatRow& r = args.row[i];
+        double mx;
+        if (r.f32) { const uint32_t b = (uint32_t)h[i * 4]; float v; memcpy(&v, &b, 4); mx = v; }
+        else { const uint16_t b = (uint16_t)h[i * 4]; _Float16 v; memcpy(&v, &b, 2); mx = (double)(float)v; }
+        h_stats[i * 5] = mx;
+        for (int k = 1; k < 4; k++) h_stats[i * 5 + k] = (double)h[i * 4 + k];
+        h_stats[i * 5 + 4] = (double)(r.f32 ? r.items : r.items * 8);
+    }
+    return LM_OK;
+}
 
 // launches layer `li`: input planes per the recipe; `out` (EPI_PO / EPI_TC) with an optional pooled copy, or the T rows (EPI_T)
 // EPI_V layers: vmode 1 (text mask + reconstruction + diff; rec4 may be null) or 2 (output logit)
@@ -951,6 +1112,9 @@ static int lm_f2_run(LmFcn2* f, int li, const LmF2Tensor* out, const LmF2Tensor*
     a.H = in.H; a.W = in.W;         // a convolution's output grid is its input grid; EPI_TC bounds its stores by the input grid
     a.tiles_x = (in.W + 16 * l.nc - 1) / (16 * l.nc);
     a.act = act;
+    a.wscale = ldexpf(1.0f, f->wexp[li]);
+    a.oscale = out ? ldexpf(1.0f, -f->texp[(int)(out - f->t)]) : 1.0f;
+    if (out && pool && f->texp[(int)(pool - f->t)] != f->texp[(int)(out - f->t)]) { lm_set_error("lm_fcn2_forward: layer %d: the pooled copy must carry its source's exponent", li); return LM_ERR_STATE; }
     if ((l.epi == LM_G2_EPI_PO || l.epi == LM_G2_EPI_TC || l.epi == LM_G2_EPI_TC2) && act != LM_ACT_GELU) { lm_set_error("lm_fcn2: the planar-output epilogues apply GELU"); return LM_ERR_ARG; }
     if (out) {
         a.out_hi = f->arena + out->off; a.out_lo = out->lo ? a.out_hi + (long long)out->c8 * out->plane : nullptr;
@@ -1053,7 +1217,7 @@ extern "C" int lm_fcn2_forward(LmFcn2* f, const uint8_t* d_rgb, int h, int w, fl
             char* hi = f->arena + up.off;
             hipLaunchKernelGGL(lm_k_convT_border2, dim3((unsigned)std::min<long long>((nb + 255) / 256, 4096)), dim3(256), 0, st, hi,
                                up.lo ? hi + (long long)up.c8 * up.plane : nullptr, up.plane, up.Wp, up.halo, up.H, up.W, 2 * in.H, 2 * in.W, up.c8,
-                               f->layer[6 + n].d_bias, LM_ACT_GELU);
+                               f->layer[6 + n].d_bias, LM_ACT_GELU, ldexpf(1.0f, -f->texp[LM_F2_UPT0 + n]));
         }
         if ((rc = lm_f2_run(f, 11 + n, n < 4 ? &T[LM_F2_CU0 + n] : &T[LM_F2_XUP], nullptr, LM_ACT_GELU, nullptr, 0, 0, st))) return rc;
     }

@@ -58,10 +58,20 @@ class FCN_LectureNet:
             self._engine_hw = (h, w)
         return self._engine
 
+    def _calibrated(self, eng, rgb):
+        """LM_FCN_RANGE=rescale | promote: the first frame an engine sees calibrates its f16 ranges before it is answered
+        (FcnEngine.calibrate); every inference entry point of this class goes through here.  Returns eng."""
+        if eng.range_guard in ("rescale", "promote") and eng.calibration is None:
+            eng.calibrate([rgb])
+            if getattr(self, "_engine2", None) is not None:     # the second engine follows the first: rebuilt on next use
+                self._engine2.close()
+                self._engine2 = None
+        return eng
+
     # ---- inference
     def forward_logits(self, rgb_u8):
         """Extension: uint8 RGB [H,W,3] (numpy or device tensor) -> device fp32 (logit, text logit, reconstruction)."""
-        return self._get_engine(int(rgb_u8.shape[0]), int(rgb_u8.shape[1])).forward(rgb_u8)
+        return self._calibrated(self._get_engine(int(rgb_u8.shape[0]), int(rgb_u8.shape[1])), rgb_u8).forward(rgb_u8)
 
     def _resizer(self):
         if getattr(self, "_rs", None) is None:
@@ -89,6 +99,9 @@ class FCN_LectureNet:
         eng = self._get_engine(nh, nw)
         lib, be = eng.lib, eng.be
         out = be.empty((n, h, w), np.uint8)
+        if n and eng.range_guard in ("rescale", "promote") and eng.calibration is None:
+            first = rgb_frames[0] if not isinstance(rgb_frames, np.ndarray) else be.from_host(rgb_frames[0])
+            self._calibrated(eng, self._halve_on_device(first, w, h)[0] if big else first)
         # Two engines on two HIP streams, frames dealt alternately: the layers below 1/8 resolution launch 288-480 workgroups on 256 CUs and a
         # second forward pass in flight fills what one leaves idle (profiles/r04_fcn_two_streams.txt: 437 -> 475 frames/s).  Each engine has
         # its own activation arena; everything a frame touches is enqueued on its engine's stream.
@@ -100,6 +113,8 @@ class FCN_LectureNet:
                     self._engine2.close()
                 self._engine2 = fcn.FcnEngine(self.widths, self.pixel_kernel_size, self.kernel_size, self._engine_hw[0], self._engine_hw[1])
                 self._engine2.load_state_dict(self._sd)
+                if eng.calibration is not None:                 # the same exponents in both engines (a promoted engine is not planar: one stream)
+                    self._engine2.copy_calibration(eng)
                 self._engine2_hw = self._engine_hw
             if getattr(self, "_side_stream", None) is None:
                 self._side_stream = torch.cuda.Stream()
@@ -150,7 +165,7 @@ class FCN_LectureNet:
         else:
             rgb = rgb_full
         eng = self._get_engine(height, width)
-        out, text, rec = eng.forward(rgb)
+        out, text, rec = self._calibrated(eng, rgb).forward(rgb)
         lib, be = eng.lib, eng.be
         n = height * width
         resized = o_width != width
