@@ -202,6 +202,16 @@ int lm_group_render(LmGroups* g, int first, int n, uint8_t* d_out, void* stream)
  * video_segmenter.py:22-28, `binary.sum() / 255`); the float64 division by 255 stays with the caller. */
 int lm_frame_sums(const uint8_t* d_frames, int n_frames, int64_t pixels_per_frame, uint64_t* d_sums, void* stream);
 
+/* Step 04, VIDEO_SEGMENTATION_METHOD = 2 (conflict minimisation): conflicts_per_frame of the segment [start_frame, end_frame]
+ * (video_segmenter.py:206-278).  One entry per conflicting pair of groups, in the order the reference visits them; all arrays
+ * on the device.  A pair counts in the segment iff alive_from <= end_frame && alive_until >= start_frame (both groups exist
+ * there: alive_from = the larger first frame, alive_until = the smaller last frame) and then adds `weight` to the frames
+ * gap_first .. gap_last (inclusive; gap_first > gap_last = none): the older group's last frame .. the newer group's first
+ * frame - 1.  d_signal[f - start_frame] is the float64 sum over the pairs IN LIST ORDER, accumulated sequentially per frame
+ * like the reference's `+=`, so it is bit-identical to it.  n_pairs == 0 (the arrays may be NULL then) writes zeros. */
+int lm_conflict_signal(const int32_t* d_gap_first, const int32_t* d_gap_last, const int32_t* d_alive_from, const int32_t* d_alive_until,
+                       const double* d_weight, int64_t n_pairs, int start_frame, int end_frame, double* d_signal, void* stream);
+
 /* Step 05 helper: which pairs (i < j) of n images placed in the frame share an ink pixel?  Replaces the all-pairs
  * ConnectedComponent.getOverlapFMeasure loop of CCStabilityEstimator.compute_overlapping_CC_groups
  * (AccessMath/preprocessing/content/cc_stability_estimator.py:696-714) and the incompatibility tests of

@@ -64,6 +64,7 @@ SIGNATURES = {
     "lm_stream_export_assign": (ctypes.c_int, [_vp, _vp, _i64, _vp]),
     "lm_stream_import_assign": (ctypes.c_int, [_vp, _vp, _i64, _vp]),
     "lm_frame_sums": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, _vp, _vp]),
+    "lm_conflict_signal": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp]),
     "speaker_detection_handle_frame": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
     "regionCumulativeDistribution": (None, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, _vp]),
     "adapthisteq": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, _vp]),

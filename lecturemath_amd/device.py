@@ -23,7 +23,7 @@ class Backend:
                 raise _lib.LecturemathLibraryError("liblecturemath_hip.so needs a GPU (torch.cuda.is_available() is False)")
             self.torch = torch
 
-    _T = {np.uint8: "uint8", np.int32: "int32", np.float32: "float32", np.int64: "int64", np.int16: "int16"}
+    _T = {np.uint8: "uint8", np.int32: "int32", np.float32: "float32", np.int64: "int64", np.int16: "int16", np.float64: "float64"}
 
     def empty(self, shape, dtype):
         if self.device:
@@ -127,6 +127,35 @@ def frame_sums(frames, lib=None):
     out = be.empty((n,), np.int64)
     lib.check(lib.lm_frame_sums(_lib.ptr(frames), n, int(frames.shape[1]) * int(frames.shape[2]), _lib.ptr(out), be.stream()))
     return be.to_host(out)
+
+
+class ConflictSignal:
+    """conflicts_per_frame of step 04's conflict-minimisation method (video_segmenter.py:206-278) for any segment of one lecture.
+
+    pairs = (gap_first, gap_last, alive_from, alive_until, weight): five equally long arrays, one entry per conflicting pair of
+    groups in the order the reference visits them (lm_conflict_signal in include/lecturemath_amd.h).  They are uploaded once;
+    signal(start, end) is one launch and one small copy per node of the recursive split."""
+
+    def __init__(self, pairs, lib=None):
+        self.lib = lib or _lib.load()
+        self.be = Backend(self.lib)
+        gap_first, gap_last, alive_from, alive_until, weight = pairs
+        host = [np.ascontiguousarray(a, np.int32) for a in (gap_first, gap_last, alive_from, alive_until)]
+        host.append(np.ascontiguousarray(weight, np.float64))
+        self.n_pairs = int(host[0].shape[0])
+        if any(a.shape != (self.n_pairs,) for a in host):
+            raise ValueError("ConflictSignal: the five pair arrays must be one-dimensional and equally long")
+        self._dev = [self.be.from_host(a) for a in host] if self.n_pairs else [None] * 5
+
+    def signal(self, start_frame, end_frame):
+        """float64 numpy array [end_frame - start_frame + 1]"""
+        n = int(end_frame) - int(start_frame) + 1
+        if n <= 0:
+            raise ValueError("ConflictSignal.signal: empty segment %d..%d" % (start_frame, end_frame))
+        out = self.be.empty((n,), np.float64)
+        self.lib.check(self.lib.lm_conflict_signal(*[_lib.ptr(a) for a in self._dev], self.n_pairs, int(start_frame), int(end_frame),
+                                                   _lib.ptr(out), self.be.stream()))
+        return self.be.to_host(out)
 
 
 def image_pairs_overlap(boxes, images, lib=None):
@@ -396,6 +425,7 @@ class Grouping:
             "arrays": A,
         }
         conf = {g: {} for g in range(ng)}
+        # lm_group_run emits the rows grouped by conf_g1, each group in the reference's first-insertion order: the inner dicts keep it
         for i in range(len(A["conf_g1"])):
             conf[int(A["conf_g1"][i])][int(A["conf_g2"][i])] = {
                 "matched": int(A["conf_matched"][i]), "unmatched": int(A["conf_unmatched"][i]),

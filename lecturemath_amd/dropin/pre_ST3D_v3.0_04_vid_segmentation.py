@@ -1,7 +1,8 @@
 """Step 04 entry point (same name, argv, config keys, inputs and output as the reference's
-pre_ST3D_v3.0_04_vid_segmentation.py) for the shipped VIDEO_SEGMENTATION_METHOD = 3 (deletion events, :44-99):
+pre_ST3D_v3.0_04_vid_segmentation.py) for VIDEO_SEGMENTATION_METHOD = 3 (deletion events, :44-99; the shipped configuration):
 [(frame_times, frame_indices, compressed_frames), (group_ages, conflicts), SpaceTimeStruct] -> list of (first, last) frame
-intervals.  The reference's debug plots (matplotlib, :100-112, :175-218) and the decompression + sums that only feed them
+intervals; and for method 2 (conflict minimisation, :114-159): [(frame_times, frame_indices, compressed_frames), (group_ages,
+conflicts)] -> the same.  Method 1 (sums + decision tree) is not built.  The reference's debug plots (matplotlib, :100-112, :175-218) and the decompression + sums that only feed them
 (:28-41) are not produced; pass the parameter `sums=1` to get the binary sums printed."""
 import sys
 import time
@@ -31,18 +32,56 @@ def deletion_signal(group_ages, st3D, add_threshold):
     return signal
 
 
+def conflict_intervals(process, n_frames, compressed_frames, group_ages, conflicts, st3D=None):
+    """Method 2 (:114-159): the reference's keys, parameter overrides (conf_w, conf_p, conf_t) and defaults.  For the area weights
+    "union" and "intersection" the reference divides every conflict's areas by the image size, in place; here the caller's dict is
+    left alone and the same division happens where the pairs are flattened (VideoSegmenter.from_group_conflicts, area_divisor).  The
+    image size comes from the first reconstructed frame, the only one decoded; a caller that hands over no reconstructed frames but the
+    SpaceTimeStruct as a third input (LecturePipeline.finish keeps the frames on the device) gets it from there: the same integer."""
+    from AccessMath.preprocessing.content.video_segmenter import VideoSegmenter
+
+    def weight_mode(param, key):
+        return int(process.params[param]) if param in process.params else process.configuration.get_int(key, 0)
+    weights = weight_mode("conf_w", "VIDEO_SEGMENTATION_CONFLICTS_WEIGHTS")
+    weights_pixels = weight_mode("conf_p", "VIDEO_SEGMENTATION_CONFLICTS_WEIGHTS_PIXELS")
+    weights_time = weight_mode("conf_t", "VIDEO_SEGMENTATION_CONFLICTS_WEIGHTS_TIME")
+    min_conflicts = process.configuration.get("VIDEO_SEGMENTATION_CONFLICTS_MIN_CONFLICTS", 3.0)
+    min_split = process.configuration.get_int("VIDEO_SEGMENTATION_CONFLICTS_MIN_SPLIT", 50)
+    min_length = process.configuration.get_int("VIDEO_SEGMENTATION_CONFLICTS_MIN_LENGTH", 25)
+    print((min_conflicts, min_split, min_length))
+    img_size = None
+    if weights in [VideoSegmenter.ConflictsAreaWeightsIntersection, VideoSegmenter.ConflictsAreaWeigthsUnion]:
+        if len(compressed_frames):
+            from AccessMath.preprocessing.content.helper import Helper
+            h, w = Helper.decompress_binary_images(compressed_frames[:1])[0].shape
+        elif st3D is not None:
+            h, w = st3D.height, st3D.width
+        else:
+            raise ValueError("VIDEO_SEGMENTATION_CONFLICTS_WEIGHTS = %d normalises the areas by the image size, which is read from the "
+                             "first reconstructed frame: none was given" % weights)
+        img_size = h * w
+    return VideoSegmenter.from_group_conflicts(n_frames, group_ages, conflicts, min_conflicts, min_split, min_length, weights,
+                                               weights_pixels, weights_time, None, area_divisor=img_size)
+
+
 def process_input(process, input_data):
     from AccessMath.data.space_time_struct import SpaceTimeStruct
     from AccessMath.preprocessing.content.video_segmenter import VideoSegmenter
     segmentation_method = process.configuration.get_int("VIDEO_SEGMENTATION_METHOD", 3)
-    if segmentation_method != 3:
-        raise NotImplementedError("only VIDEO_SEGMENTATION_METHOD = 3 (deletion events, the shipped configuration) is built")
+    if segmentation_method not in (2, 3):
+        raise NotImplementedError("VIDEO_SEGMENTATION_METHOD = %d is not built: 3 (deletion events, the shipped configuration) and "
+                                  "2 (conflict minimisation) are" % segmentation_method)
     frame_times, frame_indices, compressed_frames = input_data[0]
     if "sums" in process.params:
         from AccessMath.preprocessing.content.helper import Helper
         print("Computing sums...")
         print(VideoSegmenter.compute_binary_sums(Helper.decompress_binary_images(compressed_frames)))
     group_ages, conflicts = input_data[1]
+    if segmentation_method == 2:
+        intervals = conflict_intervals(process, len(frame_indices), compressed_frames, group_ages, conflicts,
+                                       input_data[2] if len(input_data) > 2 else None)
+        print("Total intervals: " + str(len(intervals)))
+        return intervals
     st3D = input_data[2]
     assert isinstance(st3D, SpaceTimeStruct)
     add_threshold = process.configuration.get_float("VIDEO_SEGMENTATION_DEL_EVENT_ADD_THRESHOLD", 10)
