@@ -222,6 +222,54 @@ int lm_conflict_signal(const int32_t* d_gap_first, const int32_t* d_gap_last, co
 int lm_image_pairs_overlap(const int32_t* h_boxes, const uint8_t* h_images, const int64_t* h_img_off, int n, int32_t* h_pairs,
                            int64_t cap, int64_t* n_pairs, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------------------------------
+ * Step 05 on the device (KeyframeExtractor.GenerateFromST3DForIntervals, AccessMath/preprocessing/content/
+ * keyframe_extractor.py:13-145): a table of bit-row images placed in a width x height frame.  Item = one image: its box and
+ * ceil(w / 32) 32-bit words per row, bit x & 31 of word x >> 5 = ink at column x of the box.
+ * -------------------------------------------------------------------------------------------------------------------------- */
+typedef struct LmKeyframes LmKeyframes;
+
+/* A VIEW of the group images of a finished lm_group_run: item gimg_item_off[g] + k (the numbering of LM_G_GIMG_ITEM_OFF) is
+ * segment image k of group g.  The bits are the group's own bit rows: no pixel is copied, nothing is expanded, LM_G_GIMG is not
+ * touched.  Lifetime: the bit rows are allocated from the run's device arena (or on their own when they did not fit); the arena
+ * is the stream's cached one, marked busy for as long as the LmGroups exists, and both are released only by lm_group_destroy --
+ * no per-run or per-phase arena frees them earlier.  The view is therefore valid until lm_group_destroy(g) and must be
+ * destroyed before it.  Returns NULL (lm_last_error) when g is NULL or holds no images. */
+LmKeyframes* lm_kf_create_from_group(LmGroups* g);
+
+/* The same table from host images with the conventions of lm_image_pairs_overlap (h_boxes [n][4] = min_x, max_x, min_y, max_y
+ * inclusive, h_img_off [n + 1] byte offsets into h_images, non-zero = ink): uploaded once and packed to bit rows.  Every box
+ * must lie inside the width x height frame (both <= 32768).  n == 0 gives an empty table.  NULL (lm_last_error) on failure. */
+LmKeyframes* lm_kf_create_from_images(const int32_t* h_boxes, const uint8_t* h_images, const int64_t* h_img_off, int n, int width,
+                                      int height, void* stream);
+void lm_kf_destroy(LmKeyframes* kf);
+
+/* number of items (-1 for NULL) */
+int lm_kf_count(const LmKeyframes* kf);
+
+/* For all video segments in one call: segment s lists the items h_items[h_seg_off[s] .. h_seg_off[s + 1]) (h_seg_off[0] == 0,
+ * ascending).  Writes the pairs (i < j) of list POSITIONS of one segment whose images share an ink pixel as rows
+ * (segment, i, j), sorted by all three, to h_triples [cap][3]; *n_found = rows found, LM_ERR_CAPACITY when that exceeds cap.
+ * A box join per segment (pairs never cross segments), then one bit test over all candidates.  Two stream synchronisations
+ * and no device allocation once the handle's scratch has grown to the lecture's size, whatever n_seg is; a candidate region
+ * that was guessed too small adds one round. */
+int lm_kf_overlaps(LmKeyframes* kf, const int64_t* h_seg_off, const int32_t* h_items, int n_seg, int32_t* h_triples, int64_t cap,
+                   int64_t* n_found, void* stream);
+
+/* Keyframes: d_out [n_seg][height][width][channels] uint8 on the device, channels 1 or 3 (all equal); keyframe s is 0 where any
+ * of the items h_draw_items[h_draw_off[s] .. h_draw_off[s + 1]) has ink and 255 elsewhere (the reference's 255 - frame_image,
+ * keyframe_extractor.py:131-141); an empty list gives an all-255 keyframe.  Every byte of d_out is written exactly once.
+ * Asynchronous on `stream`. */
+int lm_kf_render(LmKeyframes* kf, const int64_t* h_draw_off, const int32_t* h_draw_items, int n_seg, int channels, uint8_t* d_out,
+                 void* stream);
+
+/* One item as the reference's h x w uint8 0 / 255 image, to the host; bytes must be h * w of the item. */
+int lm_kf_image(LmKeyframes* kf, int item, uint8_t* h_out, int64_t bytes, void* stream);
+
+/* Diagnostic: (tile, keyframe) units of lm_kf_render that listed more items than the workgroup's hit list holds and composed the
+ * rest on the crowded-tile path, since the handle was created. */
+int lm_kf_crowded_tiles(LmKeyframes* kf, int64_t* h_count, void* stream);
+
 /* ---- the remaining exports of the reference's accessmath_lib.c (classical, pre-FCN binarizers) --------
  * Same symbols and C signatures as the reference, host pointers (ctypes), results bit-identical to the C library:
  *   accessmath_lib.c:7-111    speaker_detection_handle_frame (bound by AccessMath/preprocessing/video_worker/ speaker detection)

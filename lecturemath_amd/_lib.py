@@ -101,6 +101,14 @@ SIGNATURES = {
     "lm_png_encode": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _i64, _vp, _vp]),
     "lm_png_pack": (ctypes.c_int, [_vp, _i64, _vp, _vp, ctypes.c_int, _vp, _vp]),
     "lm_png_decode": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _vp, _vp, _vp]),
+    "lm_kf_create_from_group": (_vp, [_vp]),
+    "lm_kf_create_from_images": (_vp, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
+    "lm_kf_destroy": (None, [_vp]),
+    "lm_kf_count": (ctypes.c_int, [_vp]),
+    "lm_kf_overlaps": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _i64, _vp, _vp]),
+    "lm_kf_render": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    "lm_kf_image": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _i64, _vp]),
+    "lm_kf_crowded_tiles": (ctypes.c_int, [_vp, _vp, _vp]),
 }
 
 

@@ -5,6 +5,7 @@ With the test-only emulated library (tests/hipemu) "device" memory is host memor
 stand in for torch tensors; the product never selects that path by itself (see _lib.load).
 """
 import ctypes
+import weakref
 
 import numpy as np
 
@@ -180,6 +181,192 @@ def image_pairs_overlap(boxes, images, lib=None):
             continue
         lib.check(rc)
         return [(int(a), int(b)) for a, b in pairs[:int(found[0])]]
+
+
+class GroupImages:
+    """Step 05 on the device: a table of images placed in the frame, held as bit rows (lm_kf_* in include/lecturemath_amd.h).
+
+    from_grouping(grouping)   a view of the group images step 03 left on the device: item gimg_item_off[g] + k is segment image k
+                              of group g (`item_first`); nothing is copied or expanded.  The Grouping is kept alive by the view and
+                              closes the view when it is closed itself.
+    from_host(boxes, images, width, height)   host uint8 images (conventions of image_pairs_overlap), uploaded and packed once.
+    overlaps / render answer for all video segments in one call each."""
+
+    created = 0          # instances made in this process (tests assert that the host route makes none)
+
+    def __init__(self, lib, handle, width, height, shapes, owner=None, item_first=None):
+        self.lib, self.be = lib, Backend(lib)
+        self.handle, self.width, self.height = handle, int(width), int(height)
+        self._shapes = shapes                   # [n_items][2] = h, w
+        self._owner = owner
+        self.item_first = item_first
+        GroupImages.created += 1
+
+    @classmethod
+    def from_grouping(cls, grouping):
+        if getattr(grouping, "handle", None) is None:
+            raise ValueError("GroupImages.from_grouping: the Grouping is closed")
+        lib = grouping.lib
+        handle = lib.lm_kf_create_from_group(grouping.handle)
+        if not handle:
+            raise _lib.LecturemathError(_lib.LM_ERR_ARG, lib.last_error())
+        off = grouping.array("gimg_item_off")
+        b = grouping.array("bounds").reshape(-1, 4).astype(np.int64)
+        per_group = np.stack([b[:, 3] - b[:, 2] + 1, b[:, 1] - b[:, 0] + 1], axis=1)
+        self = cls(lib, handle, grouping.stream.width, grouping.stream.height, np.repeat(per_group, np.diff(off), axis=0), grouping, off[:-1].copy())
+        grouping._views.add(self)
+        return self
+
+    @classmethod
+    def from_host(cls, boxes, images, width, height, lib=None):
+        lib = lib or _lib.load()
+        n = len(images)
+        hb = np.ascontiguousarray(np.asarray(boxes, np.int32).reshape(n, 4))
+        off = np.zeros(n + 1, np.int64)
+        off[1:] = np.cumsum([im.size for im in images])
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(im, np.uint8).ravel() for im in images])) if n else np.zeros(1, np.uint8)
+        handle = lib.lm_kf_create_from_images(hb.ctypes.data if n else None, flat.ctypes.data if n else None, off.ctypes.data if n else None, n,
+                                              int(width), int(height), Backend(lib).stream())
+        if not handle:
+            raise _lib.LecturemathError(_lib.LM_ERR_ARG, lib.last_error())
+        return cls(lib, handle, width, height, np.stack([hb[:, 3] - hb[:, 2] + 1, hb[:, 1] - hb[:, 0] + 1], axis=1).astype(np.int64))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.lm_kf_destroy(self.handle)
+            self.handle = None
+        self._owner = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __reduce__(self):
+        raise TypeError("GroupImages is a handle to device memory and cannot be pickled")
+
+    def __len__(self):
+        return int(self.lib.lm_kf_count(self._live()))
+
+    def _live(self):
+        if getattr(self, "handle", None) is None:
+            raise ValueError("GroupImages: the handle is closed")
+        return self.handle
+
+    @staticmethod
+    def _csr(lists):
+        off = np.zeros(len(lists) + 1, np.int64)
+        off[1:] = np.cumsum([len(lst) for lst in lists])
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(lst, np.int32).reshape(-1) for lst in lists])) if off[-1] else np.zeros(1, np.int32)
+        return off, flat
+
+    def overlaps(self, item_lists):
+        """item_lists: one list of items per video segment -> per segment the sorted pairs (i < j) of list positions whose images
+        share an ink pixel."""
+        handle = self._live()
+        off, flat = self._csr(item_lists)
+        cap = max(1024, 8 * int(off[-1]))
+        while True:
+            triples = np.zeros((cap, 3), np.int32)
+            found = np.zeros(1, np.int64)
+            rc = self.lib.lm_kf_overlaps(handle, off.ctypes.data, flat.ctypes.data, len(item_lists), triples.ctypes.data, cap, found.ctypes.data,
+                                         self.be.stream())
+            if rc == _lib.LM_ERR_CAPACITY and int(found[0]) > cap:
+                cap = int(found[0])
+                continue
+            self.lib.check(rc)
+            break
+        out = [[] for _ in item_lists]
+        for s, i, j in triples[:int(found[0])].tolist():
+            out[s].append((i, j))
+        return out
+
+    def render(self, draw_lists, channels=3, out=None):
+        """One keyframe per list: device uint8 [len(draw_lists), height, width, channels], 0 where a listed item has ink, else 255."""
+        handle = self._live()
+        off, flat = self._csr(draw_lists)
+        shape = (len(draw_lists), self.height, self.width, int(channels))
+        if out is None:
+            out = self.be.empty(shape, np.uint8)
+        elif tuple(out.shape) != shape:
+            raise ValueError("GroupImages.render: out has shape %s, expected %s" % (tuple(out.shape), shape))
+        self.lib.check(self.lib.lm_kf_render(handle, off.ctypes.data, flat.ctypes.data, len(draw_lists), int(channels), _lib.ptr(out), self.be.stream()))
+        return out
+
+    def image(self, item):
+        """item as the reference's uint8 0 / 255 array (h, w)"""
+        handle = self._live()
+        if not 0 <= int(item) < len(self._shapes):
+            raise IndexError("GroupImages.image: item %d of %d" % (item, len(self._shapes)))
+        h, w = (int(v) for v in self._shapes[int(item)])
+        out = np.zeros((h, w), np.uint8)
+        self.lib.check(self.lib.lm_kf_image(handle, int(item), out.ctypes.data, h * w, self.be.stream()))
+        return out
+
+    def crowded_tiles(self):
+        """(tile, keyframe) units of render() that took the crowded-tile path so far"""
+        n = np.zeros(1, np.int64)
+        self.lib.check(self.lib.lm_kf_crowded_tiles(self._live(), n.ctypes.data, self.be.stream()))
+        return int(n[0])
+
+
+class _LazyImageList:
+    """cc_group_images[g]: len() and [k] backed by GroupImages.image, nothing held"""
+
+    def __init__(self, gi, first, count):
+        self._gi, self._first, self._count = gi, int(first), int(count)
+
+    def __len__(self):
+        return self._count
+
+    def __getitem__(self, k):
+        if isinstance(k, slice):
+            return [self[i] for i in range(*k.indices(self._count))]
+        k = int(k)
+        if k < 0:
+            k += self._count
+        if not 0 <= k < self._count:
+            raise IndexError("list index out of range")
+        return self._gi.image(self._first + k)
+
+    def __iter__(self):
+        return (self[k] for k in range(self._count))
+
+
+class LazyGroupImages:
+    """Read-only stand-in for SpaceTimeStruct.cc_group_images ({group: [uint8 image per age segment]}) over a GroupImages view:
+    an image is expanded when it is indexed.  Pickles as the plain dict of lists it stands for."""
+
+    def __init__(self, gi, item_off):
+        self._gi = gi
+        self._off = np.asarray(item_off, np.int64)          # [n_groups + 1]
+
+    def __len__(self):
+        return len(self._off) - 1
+
+    def __iter__(self):
+        return iter(range(len(self)))
+
+    def __contains__(self, g):
+        return isinstance(g, (int, np.integer)) and 0 <= g < len(self)
+
+    def keys(self):
+        return range(len(self))
+
+    def __getitem__(self, g):
+        if g not in self:
+            raise KeyError(g)
+        return _LazyImageList(self._gi, self._off[g], self._off[g + 1] - self._off[g])
+
+    def values(self):
+        return (self[g] for g in self)
+
+    def items(self):
+        return ((g, self[g]) for g in self)
+
+    def __reduce__(self):
+        return (dict, ({g: list(self[g]) for g in self},))
 
 
 def decode_crop(words, min_x, max_x, min_y, max_y):
@@ -370,11 +557,14 @@ class Grouping:
         self.lib, self.be = stream.lib, stream.be
         self.handle = self.lib.lm_group_run(stream.handle, max_gap, min_times, t_window, min_recall, img_threshold,
                                             1 if reconstruct else 0, self.be.stream())
+        self._views = weakref.WeakSet()         # GroupImages views of this run's bit rows: closed before the run is destroyed
         if not self.handle:
             raise _lib.LecturemathError(_lib.LM_ERR_HIP, self.lib.last_error())
 
     def close(self):
         if getattr(self, "handle", None):
+            for view in list(self._views):
+                view.close()
             self.lib.lm_group_destroy(self.handle)
             self.handle = None
 

@@ -12,6 +12,12 @@ class SpaceTimeStruct:
         self.cc_group_images = group_images
         self.cc_group_boundaries = group_boundaries
 
+    # what LecturePipeline.finish(keyframes="device") attaches: handles to device memory, never part of the pickled structure
+    _DEVICE_ATTRIBUTES = ("_device_images", "_device_keyframes")
+
+    def __getstate__(self):
+        return {k: v for k, v in self.__dict__.items() if k not in self._DEVICE_ATTRIBUTES}
+
     def groups_in_frame_range(self, frame_start, frame_end, group_list=None):
         groups = list(self.cc_group_ages.keys()) if group_list is None else group_list
         return [g for g in groups

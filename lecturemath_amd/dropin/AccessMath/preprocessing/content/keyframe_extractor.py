@@ -18,7 +18,17 @@ The reference takes the position from `list(set)` of a component that was assemb
 iteration order for small ints, which is NOT ascending once values exceed the table size ({5, 300} iterates as 300, 5) and
 depends on the sequence of unions.  Groups of one component that start at the same frame and overlap are therefore resolved by
 that order; `_component_member_order` reproduces it by performing the same unions on real Python sets, in the sequence the
-reference's scan produces (ascending object, ascending partner), and nothing else of it."""
+reference's scan produces (ascending object, ascending partner), and nothing else of it.
+
+Device route (GenerateFromGroupImages).  When the group images already are bit rows on the device
+(lecturemath_amd.device.GroupImages) the step is four passes: (1) host: per segment the alive groups and the image chosen for
+each; (2) device: ONE overlaps call for all segments; (3) host: the component order and the greedy walk above, unchanged --
+it is sequential, order-dependent and a few hundred objects; (4) device: ONE render call for all keyframes.
+GenerateFromST3DForIntervals takes that route when the structure carries a live GroupImages (`_device_images`, set by
+LecturePipeline.finish(keyframes="device"), never pickled) or when LM_KEYFRAMES=device is set (read at every call, default
+"host"): then the images any segment selects are uploaded once (GroupImages.from_host)."""
+import os
+
 import numpy as np
 
 from AccessMath.data.space_time_struct import SpaceTimeStruct
@@ -52,9 +62,113 @@ class KeyframeExtractor:
         return components, isolated
 
     @staticmethod
+    def _drawn_objects(n, pairs, first_of, ids, seg_no, verbose):
+        """Step 3 of the module docstring for one segment: n alive objects, their overlapping pairs (i < j, sorted), the first frame
+        of each.  Returns (objects drawn, isolated objects, components)."""
+        clash = np.zeros((n, n), dtype=bool)
+        if len(pairs):
+            pa = np.asarray(pairs, dtype=np.int64)
+            clash[pa[:, 0], pa[:, 1]] = clash[pa[:, 1], pa[:, 0]] = True
+        components, isolated = KeyframeExtractor._component_member_order(n, pairs)
+        drawn = list(isolated)
+        for comp in components:
+            # most recently started first; equal starts: later position in the component first
+            order = sorted(range(len(comp)), key=lambda pos: (first_of[comp[pos]], pos), reverse=True)
+            kept = []
+            for pos in order:
+                if not clash[comp[pos], kept].any():
+                    kept.append(comp[pos])
+            drawn.extend(kept)
+            if verbose:
+                print("  segment %d: %d overlapping groups, keeping %s" % (seg_no + 1, len(comp), ",".join(str(ids[o]) for o in kept)))
+        return drawn, isolated, components
+
+    @staticmethod
+    def _segment_selection(group_ages, video_segments):
+        """Pass 1: (group_ids, first frame per group, per segment (alive positions in group_ids, image index k of each))."""
+        group_ids = list(group_ages)
+        first = np.array([group_ages[g][0] for g in group_ids], dtype=np.int64)
+        last = np.array([group_ages[g][-1] for g in group_ids], dtype=np.int64)
+        selection = []
+        for seg_first, seg_last in video_segments:
+            alive = np.flatnonzero((seg_first <= last) & (first <= seg_last))
+            ks = []
+            for a in alive:
+                ages = group_ages[group_ids[a]]
+                if len(ages) < 2:
+                    raise IndexError("list index out of range")       # no segment image: what cc_group_images[g][0] raises
+                # segment image k covers [ages[k], ages[k + 1]]: the last one whose end lies inside the video segment, else the first
+                ks.append(max(0, int(np.searchsorted(ages, seg_last, side="right")) - 2))
+            selection.append((alive, ks))
+        return group_ids, first, selection
+
+    @staticmethod
+    def _from_selection(gi, item_of, group_ids, first, selection, group_boundaries, frame_times, video_segments, verbose, device_frames):
+        """Passes 2-4 over a GroupImages; item_of(group, k) names the item of a selected image."""
+        item_lists = [[item_of(group_ids[a], k) for a, k in zip(alive, ks)] for alive, ks in selection]
+        pairs_per_segment = gi.overlaps(item_lists)
+        draw_lists, keyframe_times = [], []
+        if verbose:
+            print("%d CC groups, %d video segments" % (len(group_ids), len(video_segments)))
+        for seg_no, ((alive, ks), items, pairs) in enumerate(zip(selection, item_lists, pairs_per_segment)):
+            ids = [group_ids[a] for a in alive]
+            drawn, isolated, components = KeyframeExtractor._drawn_objects(len(ids), pairs, first[alive], ids, seg_no, verbose)
+            times = []
+            for o in drawn:
+                x0, x1, y0, y1 = (int(v) for v in group_boundaries[ids[o]])
+                times.append((frame_times[first[alive[o]]], x0, x1, y0, y1))
+            if verbose:
+                seg_first, seg_last = video_segments[seg_no]
+                print("  segment %d (%d - %d): %d groups, %d isolated, %d in %d overlapping sets" %
+                      (seg_no + 1, seg_first, seg_last, len(ids), len(isolated), sum(len(c) for c in components), len(components)))
+            draw_lists.append([items[o] for o in drawn])
+            keyframe_times.append(sorted(times))
+        frames = gi.render(draw_lists, channels=3)
+        if device_frames:
+            return frames, keyframe_times
+        return list(gi.be.to_host(frames)), keyframe_times
+
+    @staticmethod
+    def GenerateFromGroupImages(gi, item_first, group_ages, group_boundaries, frame_times, height, width, video_segments, verbose=True,
+                                device_frames=False):
+        """The keyframes from a lecturemath_amd.device.GroupImages; item_first[g] + k is segment image k of group g.  Returns what
+        GenerateFromST3DForIntervals returns; with device_frames the keyframes are ONE device uint8 tensor [n_segments, H, W, 3]."""
+        if (int(height), int(width)) != (gi.height, gi.width):
+            raise ValueError("GenerateFromGroupImages: frame %d x %d, images placed in %d x %d" % (width, height, gi.width, gi.height))
+        group_ids, first, selection = KeyframeExtractor._segment_selection(group_ages, video_segments)
+        return KeyframeExtractor._from_selection(gi, lambda g, k: int(item_first[g]) + k, group_ids, first, selection, group_boundaries,
+                                                 frame_times, video_segments, verbose, device_frames)
+
+    @staticmethod
+    def _generate_uploading(st3D, video_segments, verbose):
+        """LM_KEYFRAMES=device on a structure that holds host images: the images any segment selects, uploaded once."""
+        from lecturemath_amd import device
+        group_ids, first, selection = KeyframeExtractor._segment_selection(st3D.cc_group_ages, video_segments)
+        item = {}
+        for alive, ks in selection:
+            for a, k in zip(alive, ks):
+                item.setdefault((group_ids[a], k), len(item))
+        boxes = [tuple(int(v) for v in st3D.cc_group_boundaries[g]) for g, _ in item]
+        images = [st3D.cc_group_images[g][k] for g, k in item]
+        gi = device.GroupImages.from_host(boxes, images, st3D.width, st3D.height)
+        try:
+            return KeyframeExtractor._from_selection(gi, lambda g, k: item[(g, k)], group_ids, first, selection, st3D.cc_group_boundaries,
+                                                     st3D.frame_times, video_segments, verbose, False)
+        finally:
+            gi.close()
+
+    @staticmethod
     def GenerateFromST3DForIntervals(st3D, video_segments, verbose=True):
         from lecturemath_amd import device
         assert isinstance(st3D, SpaceTimeStruct)
+        gi = getattr(st3D, "_device_images", None)
+        if gi is not None and getattr(gi, "handle", None):
+            frames, times = KeyframeExtractor.GenerateFromGroupImages(gi, gi.item_first, st3D.cc_group_ages, st3D.cc_group_boundaries, st3D.frame_times,
+                                                                      st3D.height, st3D.width, video_segments, verbose, device_frames=True)
+            st3D._device_keyframes = frames
+            return list(gi.be.to_host(frames)), times
+        if os.environ.get("LM_KEYFRAMES", "host") == "device":
+            return KeyframeExtractor._generate_uploading(st3D, video_segments, verbose)
         group_ids = list(st3D.cc_group_ages)
         first = np.array([st3D.cc_group_ages[g][0] for g in group_ids], dtype=np.int64)
         last = np.array([st3D.cc_group_ages[g][-1] for g in group_ids], dtype=np.int64)
@@ -72,23 +186,8 @@ class KeyframeExtractor:
                 boxes.append(tuple(int(v) for v in st3D.cc_group_boundaries[g]))
                 images.append(st3D.cc_group_images[g][k])
             pairs = device.image_pairs_overlap(boxes, images)
+            drawn, isolated, components = KeyframeExtractor._drawn_objects(len(ids), pairs, first[alive], ids, seg_no, verbose)
             n = len(ids)
-            clash = np.zeros((n, n), dtype=bool)
-            if pairs:
-                pa = np.asarray(pairs, dtype=np.int64)
-                clash[pa[:, 0], pa[:, 1]] = clash[pa[:, 1], pa[:, 0]] = True
-            components, isolated = KeyframeExtractor._component_member_order(n, pairs)
-            drawn = list(isolated)
-            for comp in components:
-                # most recently started first; equal starts: later position in the component first
-                order = sorted(range(len(comp)), key=lambda pos: (first[alive[comp[pos]]], pos), reverse=True)
-                kept = []
-                for pos in order:
-                    if not clash[comp[pos], kept].any():
-                        kept.append(comp[pos])
-                drawn.extend(kept)
-                if verbose:
-                    print("  segment %d: %d overlapping groups, keeping %s" % (seg_no + 1, len(comp), ",".join(str(ids[o]) for o in kept)))
             mask = np.zeros((st3D.height, st3D.width), dtype=bool)
             times = []
             for o in drawn:

@@ -12,7 +12,9 @@ The stages are the drop-in classes and scripts themselves (lecturemath_amd/dropi
 pre_ST3D_v3.0_03/04/05 process_input), so every product is the one the step-by-step scripts give; only the hand-offs differ
 (add_frames_device / no PNG).  `out` holds: group_ages, conflicts, st3d (SpaceTimeStruct), intervals, keyframes, cc_times,
 and -- lazily, on request -- the reconstructed frames as PNG byte strings like the reference's CC_RECONSTRUCTED_OUTPUT
-(finish(reconstructed_png=True): host zlib; "device": encoded on the device, lecturemath_amd.png_device)."""
+(finish(reconstructed_png=True): host zlib; "device": encoded on the device, lecturemath_amd.png_device).
+finish(keyframes="device") keeps step 05 on the device as well: the group images stay the bit rows step 03 wrote, `out` gains
+keyframes_device (the keyframes as one device tensor; None on the host route)."""
 import importlib.util
 import os
 import sys
@@ -100,8 +102,13 @@ class LecturePipeline:
         self._stamp(n, times, indices)
 
     # ---- steps 03, 04, 05 ----------------------------------------------------------------------------------------------
-    def finish(self, reconstructed_png=False):
-        """reconstructed_png: False (none), True (host zlib, whatever LM_PNG_CODEC says) or "device" (encoded on the device)."""
+    def finish(self, reconstructed_png=False, keyframes="host"):
+        """reconstructed_png: False (none), True (host zlib, whatever LM_PNG_CODEC says) or "device" (encoded on the device).
+        keyframes: "host" expands every group image to host uint8 arrays for step 05 (the reference's data flow); "device" leaves
+        them on the device as the bit rows step 03 wrote: step 05 reads them through a device.GroupImages view, st3d.cc_group_images
+        is a lazy read-only mapping over that view, and out["keyframes_device"] is the device tensor [n_segments, H, W, 3]."""
+        if keyframes not in ("host", "device"):
+            raise ValueError("LecturePipeline.finish: keyframes must be 'host' or 'device', not %r" % (keyframes,))
         from AccessMath.data.space_time_struct import SpaceTimeStruct
         est, cfg = self.estimator, self.configuration
         est.finish_processing()
@@ -113,8 +120,19 @@ class LecturePipeline:
                                          cfg.get("CC_GROUPING_MIN_TIME_IOU", 0.25))
         group_ages, groups_per_frame = est.compute_groups_temporal_information(groups)
         conflicts = est.compute_conflicting_groups(stable, all_ov, len(groups), gid)
-        group_images, group_boundaries = est.compute_group_images(groups, group_ages, cfg.get_float("CC_GROUPING_MIN_IMAGE_THRESHOLD", 0.5))
+        img_threshold = cfg.get_float("CC_GROUPING_MIN_IMAGE_THRESHOLD", 0.5)
+        if keyframes == "device":
+            from lecturemath_amd import device
+            est._thr = float(img_threshold)
+            grouping = est._cur(est._thr)
+            group_boundaries = grouping.result(with_images=False, with_clean=False)["group_boundaries"]
+            view = device.GroupImages.from_grouping(grouping)
+            group_images = device.LazyGroupImages(view, grouping.array("gimg_item_off"))
+        else:
+            group_images, group_boundaries = est.compute_group_images(groups, group_ages, img_threshold)
         st3d = SpaceTimeStruct(self.frame_times, self.frame_indices, est.height, est.width, group_ages, group_images, group_boundaries)
+        if keyframes == "device":
+            st3d._device_images = view
         compressed = est._frames_png("device" if reconstructed_png == "device" else "host") if reconstructed_png else []
         step03 = [(self.frame_times, self.frame_indices, compressed), (group_ages, conflicts), st3d]
         import contextlib
@@ -122,8 +140,9 @@ class LecturePipeline:
         sink = contextlib.nullcontext() if self.verbose else contextlib.redirect_stdout(io.StringIO())
         with sink:
             intervals = _script("pre_ST3D_v3.0_04_vid_segmentation.py").process_input(self.process, step03)
-            (summary_indices, summary_times, keyframes), = _script("pre_ST3D_v3.0_05_generate_summary.py").process_input(self.process, [st3d, intervals])
+            (summary_indices, summary_times, summary_keyframes), = _script("pre_ST3D_v3.0_05_generate_summary.py").process_input(self.process, [st3d, intervals])
         from AccessMath.preprocessing.content.keyframe_extractor import KeyframeExtractor   # noqa: F401  (cc_times below)
-        return {"group_ages": group_ages, "conflicts": conflicts, "st3d": st3d, "intervals": intervals, "keyframes": keyframes,
-                "summary_indices": summary_indices, "summary_times": summary_times, "reconstructed_png": compressed,
+        return {"group_ages": group_ages, "conflicts": conflicts, "st3d": st3d, "intervals": intervals, "keyframes": summary_keyframes,
+                "keyframes_device": getattr(st3d, "_device_keyframes", None), "summary_indices": summary_indices, "summary_times": summary_times,
+                "reconstructed_png": compressed,
                 "reconstructed_device": lambda first, count: est.frames_from_groups_device(first, count)}
