@@ -64,6 +64,18 @@ int lm_threshold_invert(const float* d_logits, uint8_t* d_out, int64_t n, int th
  * non-inverted image (:461-467) */
 int lm_threshold(const float* d_logits, uint8_t* d_out, int64_t n, int thr, int invert, void* stream);
 
+/* FCN heads -> the byte images of FCN_LectureNet.binarize (FCN_lecturenet.py:452-479, 534-555), one pass.
+   d_logit / d_text: fp32 [n_px] or NULL, each with its destination d_binary / d_text_u8 (uint8 [n_px]).
+   d_rec: fp32 [3][n_px] (planes R, G, B in [-1, 1]) or NULL, with d_rec_bgr uint8 [n_px][3] (B, G, R).
+   flags: LM_FB_SOFT   1  bytes are trunc(sigmoid(x) * 255); otherwise {0, 255} by `thr`, like lm_threshold
+          LM_FB_INVERT 2  d_binary only: 255 - value (the worker's ink = 255)
+   Every present buffer 16-byte aligned and (with d_rec) n_px % 4 == 0: the vector kernel; otherwise a scalar kernel writes the same
+   bytes.  NaN inputs give unspecified bytes, as in the reference (astype(uint8)). */
+#define LM_FB_SOFT 1
+#define LM_FB_INVERT 2
+int lm_fcn_bytes(const float* d_logit, const float* d_text, const float* d_rec, int64_t n_px, int thr, int flags,
+                 uint8_t* d_binary, uint8_t* d_text_u8, uint8_t* d_rec_bgr, void* stream);
+
 /* scipy.ndimage.label (labeler.py:126) for n_frames frames (uint8, non-zero = foreground, contiguous
  * [n_frames][height][width]).  d_labels (int32, same shape) may be NULL when only the CC records are
  * wanted.  Leaves the run structures of the batch in the workspace for the calls below. */

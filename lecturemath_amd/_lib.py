@@ -13,6 +13,7 @@ DEFAULT_PATH = os.path.join(_HERE, "liblecturemath_hip.so")
 
 LM_OK, LM_ERR_ARG, LM_ERR_HIP, LM_ERR_CAPACITY, LM_ERR_STATE = 0, 1, 2, 3, 4
 LM_PNG_OK, LM_PNG_UNSUPPORTED, LM_PNG_CORRUPT = 0, 1, 2
+LM_FB_SOFT, LM_FB_INVERT = 1, 2          # flags of lm_fcn_bytes
 
 
 class LecturemathLibraryError(RuntimeError):
@@ -40,6 +41,7 @@ SIGNATURES = {
     "lm_ctx_destroy": (None, [_vp]),
     "lm_threshold_invert": (ctypes.c_int, [_vp, _vp, _i64, ctypes.c_int, _vp]),
     "lm_threshold": (ctypes.c_int, [_vp, _vp, _i64, ctypes.c_int, ctypes.c_int, _vp]),
+    "lm_fcn_bytes": (ctypes.c_int, [_vp, _vp, _vp, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),
     "lm_label_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp]),
     "lm_label_counts": (ctypes.c_int, [_vp, _vp, _vp]),
     "lm_cc_stats_batch": (ctypes.c_int, [_vp, _vp]),

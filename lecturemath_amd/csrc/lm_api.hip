@@ -11,6 +11,7 @@
 #include "../../include/lecturemath_amd.h"
 
 #include "lm_cc_kernels.hip"
+#include "lm_fcn_bytes.hip"
 #include "lm_match_kernels.hip"
 #include "lm_match_batch.hip"
 #include "lm_group.hip"
@@ -235,24 +236,37 @@ static int lm_threshold_edge(int thr, hipStream_t st, float* edge, int* state)
     return LM_OK;
 }
 
+// Which form a thresholding call takes: the comparison x >= *edge (*cmp = 1) needs buffers that qualify for the caller's vector kernel, a
+// threshold the sigmoid can straddle and a verified x* (lm_threshold_edge; its first use per threshold value synchronises the stream
+// once); everything else, and LM_THRESHOLD_FORMULA, keeps the per-pixel formula lm_thr_px (*cmp = 0).  lm_threshold, lm_fcn_bytes and
+// lm_label_batch_logits all decide here.
+static int lm_threshold_form(bool buffers_ok, int thr, hipStream_t st, float* edge, int* cmp)
+{
+    *edge = 0.0f;
+    *cmp = 0;
+    if (buffers_ok && thr >= 1 && thr <= 255 && !getenv("LM_THRESHOLD_FORMULA")) {
+        int state = 0;
+        const int rc = lm_threshold_edge(thr, st, edge, &state);
+        if (rc) return rc;
+        *cmp = state == 1;
+    }
+    return LM_OK;
+}
+
 extern "C" int lm_threshold(const float* d_logits, uint8_t* d_out, int64_t n, int thr, int invert, void* stream)
 {
     if (!d_logits || !d_out || n < 0) { lm_set_error("lm_threshold: bad arguments"); return LM_ERR_ARG; }
     if (n == 0) return LM_OK;
     const bool aligned = ((((uintptr_t)d_logits) & 15) == 0) && ((((uintptr_t)d_out) & 15) == 0);
     float edge = 0.0f;
-    // the comparison form needs a threshold the sigmoid can straddle and 16-byte aligned buffers; its first use per threshold
-    // value synchronises the stream once
-    if (aligned && thr >= 1 && thr <= 255 && !getenv("LM_THRESHOLD_FORMULA")) {
-        int state = 0;
-        const int rc = lm_threshold_edge(thr, (hipStream_t)stream, &edge, &state);
-        if (rc) return rc;
-        if (state == 1) {
-            hipLaunchKernelGGL(lm_k_threshold_cmp, dim3(lm_blocks((n + 4095) / 4096, 1, 1 << 20)), dim3(256), 0, (hipStream_t)stream, d_logits, d_out,
-                               (long long)n, edge, invert ? 0xffu : 0u);
-            LM_HIP(hipGetLastError());
-            return LM_OK;
-        }
+    int cmp = 0;
+    const int rc = lm_threshold_form(aligned, thr, (hipStream_t)stream, &edge, &cmp);
+    if (rc) return rc;
+    if (cmp) {
+        hipLaunchKernelGGL(lm_k_threshold_cmp, dim3(lm_blocks((n + 4095) / 4096, 1, 1 << 20)), dim3(256), 0, (hipStream_t)stream, d_logits, d_out,
+                           (long long)n, edge, invert ? 0xffu : 0u);
+        LM_HIP(hipGetLastError());
+        return LM_OK;
     }
     hipLaunchKernelGGL(lm_k_threshold_invert, dim3(lm_blocks((n + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream,
                        d_logits, d_out, (long long)n, thr, invert ? 0xffu : 0u);
@@ -263,6 +277,59 @@ extern "C" int lm_threshold(const float* d_logits, uint8_t* d_out, int64_t n, in
 extern "C" int lm_threshold_invert(const float* d_logits, uint8_t* d_out, int64_t n, int thr, void* stream)
 {
     return lm_threshold(d_logits, d_out, n, thr, 1, stream);
+}
+
+// the vector kernel of lm_fcn_bytes for the pairs present (have: bit 0 logit, bit 1 text, bit 2 rec; never 0)
+template <int MODE>
+static void lm_fcn_bytes_launch(int have, dim3 grid, hipStream_t st, const float* d_logit, const float* d_text, const float* d_rec, long long n, float edge, int thr,
+                                unsigned flip, uint8_t* d_binary, uint8_t* d_text_u8, uint8_t* d_rec_bgr)
+{
+#define LM_FB_CASE(H) \
+    case H: hipLaunchKernelGGL((lm_k_fcn_bytes<MODE, H>), grid, dim3(256), 0, st, d_logit, d_text, d_rec, n, edge, thr, flip, d_binary, d_text_u8, d_rec_bgr); break
+    switch (have) { LM_FB_CASE(1); LM_FB_CASE(2); LM_FB_CASE(3); LM_FB_CASE(4); LM_FB_CASE(5); LM_FB_CASE(6); LM_FB_CASE(7); }
+#undef LM_FB_CASE
+}
+
+// The byte images of FCN_LectureNet.binarize from the three heads in one pass (kernels: lm_fcn_bytes.hip).  The vector kernel needs every
+// present source and destination 16-byte aligned and, for the planes of d_rec at d_rec + n_px and d_rec + 2 n_px, n_px % 4 == 0; any
+// other call takes the scalar kernel as a whole.  Hard bytes are lm_threshold's: the same form decision, the same x*.
+extern "C" int lm_fcn_bytes(const float* d_logit, const float* d_text, const float* d_rec, int64_t n_px, int thr, int flags, uint8_t* d_binary,
+                            uint8_t* d_text_u8, uint8_t* d_rec_bgr, void* stream)
+{
+    if ((!d_logit != !d_binary) || (!d_text != !d_text_u8) || (!d_rec != !d_rec_bgr) || (!d_logit && !d_text && !d_rec) || n_px < 0 ||
+        (flags & ~(LM_FB_SOFT | LM_FB_INVERT))) {
+        lm_set_error("lm_fcn_bytes: bad arguments (every source needs its destination and the reverse, at least one pair, n_px >= 0, flags in %d)",
+                     LM_FB_SOFT | LM_FB_INVERT);
+        return LM_ERR_ARG;
+    }
+    if (n_px == 0) return LM_OK;
+    const uintptr_t bits = (uintptr_t)d_logit | (uintptr_t)d_text | (uintptr_t)d_rec | (uintptr_t)d_binary | (uintptr_t)d_text_u8 | (uintptr_t)d_rec_bgr;
+    const bool vec = (bits & 15) == 0 && (!d_rec || (n_px & 3) == 0);
+    const hipStream_t st = (hipStream_t)stream;
+    const unsigned flip = (flags & LM_FB_INVERT) ? 0xffu : 0u;
+    const long long n = (long long)n_px;
+    float edge = 0.0f;
+    int cmp = 0;
+    if (!(flags & LM_FB_SOFT)) {
+        const int rc = lm_threshold_form(vec, thr, st, &edge, &cmp);
+        if (rc) return rc;
+    }
+    const int mode = (flags & LM_FB_SOFT) ? LM_FB_SOFT_BYTES : (cmp ? LM_FB_HARD_CMP : LM_FB_HARD_FORMULA);
+    if (vec) {
+        const dim3 grid(lm_blocks((n / 16 + 255) / 256, 1, 1 << 20));
+        const int have = (d_logit ? 1 : 0) | (d_text ? 2 : 0) | (d_rec ? 4 : 0);
+        if (mode == LM_FB_HARD_CMP) lm_fcn_bytes_launch<LM_FB_HARD_CMP>(have, grid, st, d_logit, d_text, d_rec, n, edge, thr, flip, d_binary, d_text_u8, d_rec_bgr);
+        else if (mode == LM_FB_HARD_FORMULA) lm_fcn_bytes_launch<LM_FB_HARD_FORMULA>(have, grid, st, d_logit, d_text, d_rec, n, edge, thr, flip, d_binary, d_text_u8, d_rec_bgr);
+        else lm_fcn_bytes_launch<LM_FB_SOFT_BYTES>(have, grid, st, d_logit, d_text, d_rec, n, edge, thr, flip, d_binary, d_text_u8, d_rec_bgr);
+    } else {
+        const dim3 grid(lm_blocks(n, 256));
+        if (mode == LM_FB_SOFT_BYTES)
+            hipLaunchKernelGGL(lm_k_fcn_bytes_scalar<LM_FB_SOFT_BYTES>, grid, dim3(256), 0, st, d_logit, d_text, d_rec, n, thr, flip, d_binary, d_text_u8, d_rec_bgr);
+        else
+            hipLaunchKernelGGL(lm_k_fcn_bytes_scalar<LM_FB_HARD_FORMULA>, grid, dim3(256), 0, st, d_logit, d_text, d_rec, n, thr, flip, d_binary, d_text_u8, d_rec_bgr);
+    }
+    LM_HIP(hipGetLastError());
+    return LM_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -398,13 +465,13 @@ extern "C" int lm_label_batch_logits(LmCtx* c, const float* d_logits, int n_fram
     }
     const LmGeom g = c->g;
     float edge = 0.0f;
-    int state = 0;
+    int cmp = 0;
     const bool shape_ok = (g.W & 3) == 0 && ((((uintptr_t)d_logits) & 15) == 0) && (!d_binary || ((((uintptr_t)d_binary) & 3) == 0));
-    if (shape_ok && thr >= 1 && thr <= 255 && !getenv("LM_THRESHOLD_FORMULA") && !getenv("LM_LABEL_UNFUSED")) {
-        const int rc = lm_threshold_edge(thr, (hipStream_t)stream, &edge, &state);
+    {
+        const int rc = lm_threshold_form(shape_ok && !getenv("LM_LABEL_UNFUSED"), thr, (hipStream_t)stream, &edge, &cmp);
         if (rc) return rc;
     }
-    if (state == 1) {
+    if (cmp) {
         LmLabelSrc src = {nullptr, d_logits, edge, invert ? 0xffu : 0u, d_binary};
         return lm_label_batch_src(c, src, n_frames, d_labels, stream);
     }

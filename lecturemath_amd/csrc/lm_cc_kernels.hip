@@ -26,11 +26,16 @@ extern char* lm_emu_dynsmem;
 // binary = ((uint8)(sigmoid(x) * 255.0f) >= thr) ? 255 : 0 ; out = 255 - binary
 // sigmoid(x) = 1 / (1 + exp(-x)) in fp32; see DESIGN.md "threshold edge" for the ulp discussion.
 // ------------------------------------------------------------------------------------------------
-LM_DEV unsigned lm_thr_px(float x, int thr, unsigned flip)
+LM_DEV unsigned lm_sigmoid_u8(float x)   // the soft byte of binarize (force_binary=False), and what the threshold is applied to
 {
     float s = 1.0f / (1.0f + expf(-x));
     float v = s * 255.0f;
-    unsigned u = (unsigned)v;            // truncation, v in [0, 255]
+    return (unsigned)v;                  // truncation, v in [0, 255]
+}
+
+LM_DEV unsigned lm_thr_px(float x, int thr, unsigned flip)
+{
+    unsigned u = lm_sigmoid_u8(x);
     return ((u >= (unsigned)thr) ? 255u : 0u) ^ flip;   // flip = 0xff: the worker's 255 - binary
 }
 

@@ -1,7 +1,8 @@
 """FCN_LectureNet inference on the MI355X with the reference's API (lecturenet_v1/FCN_lecturenet.py):
 CreateFromConfig :620-659, load_state_dict / eval / cuda (torch.nn.Module methods the callers use,
 pre_ST3D_v3.0_01_binarize.py:30-37, test_FCN_binarizer.py:38-46), binarize :430-505, prepare_image :607-618,
-from_img_space_to_cv2 :534-555.  The convolution stack runs in liblecturemath_hip.so (lm_fcn.hip); training-only members
+from_img_space_to_cv2 :534-555.  The convolution stack runs in liblecturemath_hip.so (lm_fcn.hip, lm_fcn2.hip) and so does the conversion of its
+heads to the byte images binarize returns (lm_fcn_bytes.hip, through binarize_device); training-only members
 of the reference class are not provided (inference path only, SURVEY.md section 2 #7b/#23)."""
 import numpy as np
 import PIL.Image
@@ -145,6 +146,48 @@ class FCN_LectureNet:
             be.torch.cuda.current_stream().wait_stream(self._side_stream)
         return out
 
+    def _byte_images(self, rgb_u8, return_others, force_binary, binary_treshold, invert, out_size=None):
+        """binarize_device's work: (binary, text | None, rec | None, flat) on the device at out_size = (width, height) (default: the
+        input's), the images being views of the allocation `flat` (fcn.carve_byte_images): one copy of it is all a host caller needs."""
+        height, width = int(rgb_u8.shape[0]), int(rgb_u8.shape[1])
+        o_width, o_height = out_size or (width, height)
+        nw, nh = width, height
+        while nw * nh > FCN_LectureNet.MAX_PIXELS:
+            nw, nh = int(nw / 2), int(nh / 2)
+        resized = o_width != nw
+        if resized and not force_binary:
+            raise NotImplementedError("INTER_CUBIC upsampling of non-binary outputs (:487-492) is not implemented")
+        eng = self._get_engine(nh, nw)
+        rgb = eng.be.from_host(rgb_u8) if isinstance(rgb_u8, np.ndarray) else rgb_u8
+        if (nw, nh) != (width, height):
+            # the whole > 2.5 MP branch on the device: LANCZOS halving(s), network, byte images, NEAREST enlargement
+            rgb, _, _ = self._halve_on_device(rgb, width, height)
+        out, text, rec = self._calibrated(eng, rgb).forward(rgb)
+        small = eng.byte_images(out, text if return_others else None, rec if return_others else None, threshold=binary_treshold,
+                                soft=not force_binary, invert=invert, with_buffer=True)
+        if not resized:
+            return small
+        carved = fcn.carve_byte_images(eng.be, o_height, o_width, return_others, return_others)
+        for src, dst in zip(small[:3], carved[1:]):
+            if src is not None:
+                self._resizer().nearest(src, o_width, o_height, out=dst)
+        return carved[1:] + carved[:1]
+
+    def binarize_device(self, rgb_u8, return_others=False, force_binary=False, binary_treshold=128, invert=False, host=False):
+        """Extension: binarize() without leaving the device.  rgb_u8: uint8 RGB [H,W,3], numpy or device tensor -> device uint8 binary [H,W]
+        (with return_others: binary, text_mask [H,W], rec_img [H,W,3] in B G R order) at the input's size: the network's heads go through
+        one lm_fcn_bytes pass (:452-479, :534-555); frames above 2.5 MP are halved (:434-437 LANCZOS) and enlarged (:481-494 NEAREST) on
+        the device.  invert: binary is 255 - value, the step-01 worker's ink = 255 (FCN_lecturenet_binarizer.py:54).  force_binary=False
+        above 2.5 MP raises NotImplementedError (INTER_CUBIC).  host=True: returns (device result, the same as numpy arrays), the latter
+        brought over with ONE device-to-host copy."""
+        images = self._byte_images(rgb_u8, return_others, force_binary, binary_treshold, invert)
+        dev = images[:3] if return_others else images[0]
+        if not host:
+            return dev
+        h, w = int(rgb_u8.shape[0]), int(rgb_u8.shape[1])
+        on_host = fcn.split_byte_images(self._engine.be.to_host(images[3]), h, w, return_others, return_others)
+        return dev, (on_host if return_others else on_host[0])
+
     def binarize(self, PIL_image, return_others=False, force_binary=False, binary_treshold=128, apply_sigmoid=True):
         o_width, o_height = PIL_image.size
         width, height = o_width, o_height
@@ -156,6 +199,15 @@ class FCN_LectureNet:
                 PIL_image = PIL_image.resize((int(width / 2), int(height / 2)), Image.LANCZOS)
                 width, height = PIL_image.size
         rgb_full = np.asarray(PIL_image.convert("RGB"), dtype=np.uint8)
+        if apply_sigmoid:
+            # the byte images are made on the device (binarize_device); one copy brings them to the host, no fp32 array crosses
+            images = self._byte_images(rgb_full, return_others, force_binary, binary_treshold, False, out_size=(o_width, o_height))
+            on_host = fcn.split_byte_images(self._engine.be.to_host(images[3]), o_height, o_width, return_others, return_others)
+            return on_host if return_others else on_host[0]
+        return self._binarize_raw(rgb_full, width, height, o_width, o_height, return_others, force_binary, binary_treshold)
+
+    def _binarize_raw(self, rgb_full, width, height, o_width, o_height, return_others, force_binary, binary_treshold):
+        """apply_sigmoid=False: (logit * 255).astype(uint8) of unbounded floats, numpy's cast on the host as in the reference"""
         eng0_be = None
         if width * height > FCN_LectureNet.MAX_PIXELS:
             # the whole > 2.5 MP branch on the device: one upload of the frame, LANCZOS halving(s), network, threshold, NEAREST enlargement
@@ -166,28 +218,18 @@ class FCN_LectureNet:
             rgb = rgb_full
         eng = self._get_engine(height, width)
         out, text, rec = self._calibrated(eng, rgb).forward(rgb)
-        lib, be = eng.lib, eng.be
-        n = height * width
+        be = eng.be
         resized = o_width != width
         if resized and not force_binary:
             raise NotImplementedError("INTER_CUBIC upsampling of non-binary outputs (:487-492) is not implemented")
 
-        def enlarge(dev_u8):
-            return self._resizer().nearest(dev_u8, o_width, o_height) if resized else dev_u8
-
         def post(logits):
-            if force_binary and apply_sigmoid:
-                dst = be.empty((height, width), np.uint8)
-                lib.check(lib.lm_threshold(_lib.ptr(logits), _lib.ptr(dst), n, int(binary_treshold), 0, be.stream()))
-                return be.to_host(enlarge(dst))
             v = be.to_host(logits)
-            if apply_sigmoid:
-                v = (1.0 / (1.0 + np.exp(-v, dtype=np.float32))).astype(np.float32)
             img = (v * 255).astype(np.uint8)
             if force_binary:
                 img[img >= binary_treshold] = 255
                 img[img < binary_treshold] = 0
-            return be.to_host(enlarge(be.from_host(img))) if resized else img
+            return be.to_host(self._resizer().nearest(be.from_host(img), o_width, o_height)) if resized else img
 
         binary = post(out)
         text_mask = rec_img = None

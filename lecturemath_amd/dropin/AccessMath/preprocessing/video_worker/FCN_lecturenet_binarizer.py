@@ -30,12 +30,19 @@ class FCN_LectureNet_Binarizer:
 
     def handleFrame(self, frame, last_frame, v_index, abs_time, rel_time, abs_frame_idx):
         self.frame_count += 1
-        pil_image = PIL.Image.fromarray(frame[:, :, ::-1].copy())          # BGR -> RGB
-        binary, text_mask, rec_img = self.lecture_net.binarize(pil_image, return_others=True, force_binary=True)
-        binary = 255 - binary                                              # ink = 255 from here on
+        dev_binary = None
+        if hasattr(self.lecture_net, "binarize_device"):
+            # the device route: the kernel that makes the byte images also inverts the binary (ink = 255), one copy brings the three to the host
+            (dev_binary, _, _), (binary, text_mask, rec_img) = self.lecture_net.binarize_device(
+                frame[:, :, ::-1].copy(), return_others=True, force_binary=True, invert=True, host=True)        # BGR -> RGB
+        else:
+            pil_image = PIL.Image.fromarray(frame[:, :, ::-1].copy())          # BGR -> RGB
+            binary, text_mask, rec_img = self.lecture_net.binarize(pil_image, return_others=True, force_binary=True)
+            binary = 255 - binary                                              # ink = 255 from here on
         self.last_binary, self.last_text, self.last_rec = binary, text_mask, rec_img
         if png_device.codec() == "device":
-            self.compressed_frames.append(png_device.encode_gray8_device(binary)[0])
+            # the device frame goes to the encoder as it is (no upload); a lecture_net without the device route hands over its host array
+            self.compressed_frames.append(png_device.encode_gray8_device(binary if dev_binary is None else dev_binary)[0])
         else:
             self.compressed_frames.append(png.encode_gray8(binary))
         self.frame_indices.append(abs_frame_idx)

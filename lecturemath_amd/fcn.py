@@ -56,6 +56,25 @@ def fold_state_dict(sd):
     return folded
 
 
+def carve_byte_images(be, h, w, want_text=True, want_rec=True):
+    """One uint8 device allocation holding binary [h,w], then text [h,w], then rec [h,w,3] (the last two as asked for):
+    -> (flat, binary, text | None, rec | None), the images being views of flat.  One copy of flat brings all of them to the host
+    (split_byte_images)."""
+    n = h * w
+    flat = be.empty((n * (1 + (1 if want_text else 0) + (3 if want_rec else 0)),), np.uint8)
+    return (flat,) + split_byte_images(flat, h, w, want_text, want_rec)
+
+
+def split_byte_images(flat, h, w, want_text=True, want_rec=True):
+    """the views (binary, text | None, rec | None) of carve_byte_images' allocation, or of its copy on the host"""
+    n = h * w
+    binary = flat[:n].reshape(h, w)
+    text = flat[n:2 * n].reshape(h, w) if want_text else None
+    at = 2 * n if want_text else n
+    rec = flat[at:at + 3 * n].reshape(h, w, 3) if want_rec else None
+    return binary, text, rec
+
+
 class FcnEngine:
     """Device network built from a reference state_dict."""
 
@@ -251,3 +270,16 @@ class FcnEngine:
         out, text, rec = (self.be.empty(shape, np.float32) for shape in ((h, w), (h, w), (3, h, w)))
         self.forward_raw(_lib.ptr(rgb), h, w, _lib.ptr(out), _lib.ptr(text), _lib.ptr(rec))
         return out, text, rec
+
+    def byte_images(self, out, text, rec, threshold=128, soft=False, invert=False, with_buffer=False):
+        """The heads of forward() -> the byte images of FCN_LectureNet.binarize (:452-479, :534-555) in one lm_fcn_bytes call:
+        device uint8 (binary [H,W], text [H,W], rec [H,W,3] in B G R order), views of ONE allocation (carve_byte_images), so a caller that
+        wants them on the host makes one copy.  soft: trunc(sigmoid * 255) instead of {0, 255} by `threshold`; invert: binary is
+        255 - value (the step-01 worker's ink = 255).  text / rec may be None: not computed, None returned.  with_buffer: the flat
+        allocation comes back as a fourth value."""
+        h, w = int(out.shape[0]), int(out.shape[1])
+        flat, binary, text_u8, rec_u8 = carve_byte_images(self.be, h, w, text is not None, rec is not None)
+        flags = (_lib.LM_FB_SOFT if soft else 0) | (_lib.LM_FB_INVERT if invert else 0)
+        self.lib.check(self.lib.lm_fcn_bytes(_lib.ptr(out), _lib.ptr(text), _lib.ptr(rec), h * w, int(threshold), flags, _lib.ptr(binary), _lib.ptr(text_u8),
+                                             _lib.ptr(rec_u8), self.be.stream()))
+        return (binary, text_u8, rec_u8, flat) if with_buffer else (binary, text_u8, rec_u8)

@@ -86,12 +86,16 @@ class DeviceResizer:
                                                  _lib.ptr(bv), _lib.ptr(kv), nv, self.be.stream()))
         return out
 
-    def nearest(self, img, out_w, out_h):
-        """cv2.resize(img, (out_w, out_h), interpolation=cv2.INTER_NEAREST) for integer ratios: out[y, x] = img[y * h // out_h, x * w // out_w]"""
+    def nearest(self, img, out_w, out_h, out=None):
+        """cv2.resize(img, (out_w, out_h), interpolation=cv2.INTER_NEAREST) for integer ratios: out[y, x] = img[y * h // out_h, x * w // out_w]
+        (written into `out`, a contiguous device uint8 array of the result's shape, when given)"""
         if isinstance(img, np.ndarray):
             img = self.be.from_host(img)
         h, w = int(img.shape[0]), int(img.shape[1])
         c = 1 if len(img.shape) == 2 else int(img.shape[2])
-        out = self.be.empty((out_h, out_w) if len(img.shape) == 2 else (out_h, out_w, c), np.uint8)
+        shape =(out_h, out_w) if len(img.shape) == 2 else (out_h, out_w, c)
+        if out is None:
+            out = self.be.empty(shape, np.uint8)
+        assert tuple(int(v) for v in out.shape) == shape
         self.lib.check(self.lib.lm_upsample_nearest_u8(_lib.ptr(img), h, w, c, _lib.ptr(out), out_h, out_w, self.be.stream()))
         return out
