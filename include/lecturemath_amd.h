@@ -209,6 +209,11 @@ void lm_group_destroy(LmGroups* g);
 /* frames_from_groups (:638-681, the encoded channel 0): frames [first, first + n) -> d_out [n][height][width] uint8 */
 int lm_group_render(LmGroups* g, int first, int n, uint8_t* d_out, void* stream);
 
+/* The sums of the same frames without the frames: d_sums[i] = sum of the bytes of reconstructed frame first + i, exactly what
+ * lm_frame_sums gives on lm_group_render's output, read off the per-tile cover counts (no byte frame is written).  Same
+ * preconditions as lm_group_render; n == 0 is allowed and does nothing.  d_sums: n uint64 on the device. */
+int lm_group_frame_sums(LmGroups* g, int first, int n, uint64_t* d_sums, void* stream);
+
 /* Step 04 helper: exact per-frame sums of n_frames uint8 frames resident on the device (d_sums[f] = sum of the frame's
  * bytes).  Replaces the integer part of VideoSegmenter.compute_binary_sums (AccessMath/preprocessing/content/
  * video_segmenter.py:22-28, `binary.sum() / 255`); the float64 division by 255 stays with the caller. */

@@ -79,6 +79,7 @@ SIGNATURES = {
     "lm_group_run": (_vp, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f64, _f64, ctypes.c_int, _vp]),
     "lm_group_destroy": (None, [_vp]),
     "lm_group_render": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    "lm_group_frame_sums": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
     "lm_group_array": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
     "lm_label_batch_logits": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
     "lm_label_was_fused": (ctypes.c_int, [_vp]),

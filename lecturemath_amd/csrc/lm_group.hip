@@ -389,16 +389,15 @@ __global__ void __launch_bounds__(256) lm_k_render_items(const long long* __rest
     }
 }
 
-__global__ void __launch_bounds__(256) lm_k_render_frames(const long long* __restrict__ frame_item_off,
-                                                          const LmRenderItem* __restrict__ items, const uint32_t* __restrict__ bits,
-                                                          int first_frame, int W, int H, uint8_t* __restrict__ out)
+// The cover counts of one tile of one frame: zeroes the planes s_pl, screens the frame's items, paints those that touch the tile
+// and ends behind the barrier after which every thread may read the planes.  Shared by the kernel that writes the frame's bytes
+// (lm_k_render_frames) and the one that only sums them (lm_k_group_frame_sums).  Returns the number of items that touch the tile.
+LM_DEV int lm_render_tile(const long long* __restrict__ frame_item_off, const LmRenderItem* __restrict__ items,
+                          const uint32_t* __restrict__ bits, int f, int X0, int Y0, unsigned* s_pl)
 {
-    __shared__ unsigned s_pl[8 * LM_RT_PLANE];      // bit-sliced k per pixel (see lm_render_paint)
     __shared__ LmRenderItem s_hit[LM_RT_MAXHIT];
     __shared__ unsigned s_pre[LM_RT_MAXHIT + 1];
     __shared__ int s_nhit;
-    const int f = first_frame + blockIdx.z;
-    const int X0 = blockIdx.x * LM_RT_COLS, Y0 = blockIdx.y * LM_RT_ROWS;
     for (int i = threadIdx.x; i < 8 * LM_RT_PLANE; i += blockDim.x) s_pl[i] = 0;
     if (threadIdx.x == 0) s_nhit = 0;
     __syncthreads();
@@ -487,6 +486,16 @@ __global__ void __launch_bounds__(256) lm_k_render_frames(const long long* __res
         }
     }
     __syncthreads();
+    return s_nhit;
+}
+
+__global__ void __launch_bounds__(256) lm_k_render_frames(const long long* __restrict__ frame_item_off,
+                                                          const LmRenderItem* __restrict__ items, const uint32_t* __restrict__ bits,
+                                                          int first_frame, int W, int H, uint8_t* __restrict__ out)
+{
+    __shared__ unsigned s_pl[8 * LM_RT_PLANE];      // bit-sliced k per pixel (see lm_render_paint)
+    const int X0 = blockIdx.x * LM_RT_COLS, Y0 = blockIdx.y * LM_RT_ROWS;
+    lm_render_tile(frame_item_off, items, bits, first_frame + blockIdx.z, X0, Y0, s_pl);
     uint8_t* dst = out + (long long)blockIdx.z * W * H;
     const bool vec = ((W & 15) == 0) && ((((uintptr_t)out) & 15) == 0);
     // 16 pixels (half a plane word) -> one 16-byte store
@@ -557,6 +566,40 @@ __global__ void __launch_bounds__(256) lm_k_frame_sums(const uint8_t* __restrict
     if (lm_lane() == 0) atomicAdd(&s_acc, (unsigned long long)lo + ((unsigned long long)mid << 24) + ((unsigned long long)hi << 48));
     __syncthreads();
     if (threadIdx.x == 0 && s_acc) atomicAdd(&sums[blockIdx.y], s_acc);
+}
+
+// G5b: the same sums for the reconstructed frames, read off the cover counts of the render tile instead of bytes in HBM.  The pixel
+// under k images holds -k mod 256 = 256 * [k != 0] - k (k < 256), so a 32-pixel word of the planes b0 .. b7 adds
+// 256 * popc(b0 | .. | b7) - sum_p 2^p * popc(b_p).  A tile holds at most 64 * 256 * 255 < 2^32.  The planes are walked slot by slot,
+// the padding column (never painted: zero) included: the lanes of a wave read consecutive LDS words, one bank each.
+__global__ void __launch_bounds__(256) lm_k_group_frame_sums(const long long* __restrict__ frame_item_off,
+                                                             const LmRenderItem* __restrict__ items, const uint32_t* __restrict__ bits,
+                                                             int first_frame, int W, int H, unsigned long long* __restrict__ sums)
+{
+    __shared__ unsigned s_pl[8 * LM_RT_PLANE];      // bit-sliced k per pixel (see lm_render_paint)
+    __shared__ unsigned s_acc;
+    const int X0 = blockIdx.x * LM_RT_COLS, Y0 = blockIdx.y * LM_RT_ROWS;
+    if (threadIdx.x == 0) s_acc = 0;                // (ordered before the adds below by the barriers of lm_render_tile)
+    if (lm_render_tile(frame_item_off, items, bits, first_frame + blockIdx.z, X0, Y0, s_pl) == 0) return;      // nothing painted: adds 0
+    unsigned acc = 0;
+    for (int i = threadIdx.x; i < LM_RT_PLANE; i += blockDim.x) {
+        const int yy = i / LM_RT_PITCH, j = i - yy * LM_RT_PITCH;
+        const int y = Y0 + yy, x = X0 + 32 * j;
+        if (j >= LM_RT_COLS / 32 || y >= H || x >= W) continue;
+        const unsigned clip = (x + 32 > W) ? (0xffffffffu >> (x + 32 - W)) : 0xffffffffu;
+        unsigned any = 0, k = 0;
+#pragma unroll
+        for (int p = 0; p < 8; p++) {
+            const unsigned b = s_pl[p * LM_RT_PLANE + i] & clip;
+            any |= b;
+            k += (unsigned)__popc(b) << p;
+        }
+        acc += 256u * (unsigned)__popc(any) - k;
+    }
+    acc = lm_wave_sum(acc);
+    if (lm_lane() == 0 && acc) atomicAdd(&s_acc, acc);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_acc) atomicAdd(&sums[blockIdx.z], (unsigned long long)s_acc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1838,6 +1881,26 @@ extern "C" int lm_group_render(LmGroups* g, int first, int n, uint8_t* d_out, vo
     hipLaunchKernelGGL(lm_k_render_frames, dim3((gm.W + LM_RT_COLS - 1) / LM_RT_COLS, (gm.H + LM_RT_ROWS - 1) / LM_RT_ROWS, n), dim3(256), 0,
                        (hipStream_t)stream, g->d_frame_item_off, g->d_render_items, g->d_gbits, first, gm.W, gm.H, d_out);
     LM_HIP(hipGetLastError());
+    return LM_OK;
+}
+
+// d_sums[i] = sum of the bytes of reconstructed frame first + i (the frame lm_group_render would write), without writing it.
+extern "C" int lm_group_frame_sums(LmGroups* g, int first, int n, uint64_t* d_sums, void* stream)
+{
+    if (!g || !g->d_frame_item_off || first < 0 || n < 0 || first + n > g->n_frames || (n > 0 && !d_sums)) {
+        lm_set_error("lm_group_frame_sums: bad arguments (or lm_group_run was called with reconstruct_tables = 0)");
+        return LM_ERR_ARG;
+    }
+    if (n == 0) return LM_OK;
+    const LmGeom gm = g->s->ctx->g;
+    hipStream_t st = (hipStream_t)stream;
+    LM_HIP(hipMemsetAsync(d_sums, 0, (size_t)n * sizeof(uint64_t), st));
+    for (int f0 = 0; f0 < n; f0 += 32768) {         // (the grid's z extent ends at 65,535)
+        const int m = n - f0 < 32768 ? n - f0 : 32768;
+        hipLaunchKernelGGL(lm_k_group_frame_sums, dim3((gm.W + LM_RT_COLS - 1) / LM_RT_COLS, (gm.H + LM_RT_ROWS - 1) / LM_RT_ROWS, m), dim3(256), 0, st,
+                           g->d_frame_item_off, g->d_render_items, g->d_gbits, first + f0, gm.W, gm.H, (unsigned long long*)d_sums + f0);
+        LM_HIP(hipGetLastError());
+    }
     return LM_OK;
 }
 

@@ -592,6 +592,13 @@ class Grouping:
         self.lib.check(self.lib.lm_group_render(self.handle, first, n, _lib.ptr(out), self.be.stream()))
         return out
 
+    def frame_sums(self, first, n):
+        """Exact sums of the bytes of the reconstructed frames [first, first+n) -- frame_sums(render(first, n)) -- read off the
+        cover counts of the render tiles: no frame is written (lm_group_frame_sums).  int64 numpy."""
+        out = self.be.empty((max(int(n), 0),), np.int64)
+        self.lib.check(self.lib.lm_group_frame_sums(self.handle, first, n, _lib.ptr(out) if n > 0 else None, self.be.stream()))
+        return np.asarray(self.be.to_host(out), np.int64)
+
     def result(self, with_images=True, with_clean=True):
         """Plain-data view with the reference's names (same shape as oracle.grouping.run_step03)."""
         A = {name: self.array(i) for i, name in enumerate(_G_NAMES) if name != "gimg" or with_images}

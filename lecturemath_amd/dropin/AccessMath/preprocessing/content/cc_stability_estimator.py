@@ -255,6 +255,12 @@ class CCStabilityEstimator:
                     out.append(png.encode_gray8(frame))
         return out
 
+    def reconstructed_frame_sums(self, first=0, count=None):
+        """Extension: the exact byte sums of the reconstructed frames [first, first+count) (all from `first` on by default) as int64
+        numpy -- what frames_from_groups' frames sum to, without the frames (device.Grouping.frame_sums)."""
+        count = self.img_idx - first if count is None else count
+        return self._cur(getattr(self, "_thr", 0.5)).frame_sums(first, count)
+
     def frames_from_groups_device(self, first, count):
         """Extension: reconstructed clean frames [first, first+count) as a device uint8 tensor (no PNG)."""
         return self._cur(getattr(self, "_thr", 0.5)).render(first, count)

@@ -10,7 +10,11 @@ Method 2 rebuilds, for every node of its recursive split, the per-frame sum of t
 covers the frame.  Here the pairs are flattened once, in the reference's iteration order and with its float64 weight expression, and
 the sums come from the device (lecturemath_amd.device.ConflictSignal, lm_conflict_signal), which adds them per frame in that order:
 the signal is bit-identical to the reference's, whose peaks are decided by `>` on those sums.  lecturemath_amd is imported when the
-first signal is needed, so this module loads on its own.  The sklearn decision-tree method (1) is not part of this build."""
+first signal is needed, so this module loads on its own.
+
+Method 1 (sums + regression tree): create_regresor_from_sums (:31-40), get_tree_decision_boundaries (:43-55),
+identify_descend_intervals (:58-86), video_segments_from_erasing_intervals (:89-99), video_segments_from_sums (:102-130).  The tree is
+restated in sum_tree.py beside this file, bit-identical to the reference's sklearn regressor on these inputs; sklearn is not imported."""
 import collections.abc
 
 import numpy as np
@@ -197,8 +201,71 @@ class VideoSegmenter:
         return intervals
 
     @staticmethod
-    def video_segments_from_sums(all_sums, leaf_min, min_erase_ratio):
-        raise NotImplementedError("VIDEO_SEGMENTATION_METHOD 1 (sums + decision tree) is not part of this build; use method 3")
+    def create_regresor_from_sums(all_sums, leaf_min):
+        """The regression tree over (frame number, sum) with leaves of at least leaf_min frames (video_segmenter.py:31-40): an object
+        with predict(X), bit-identical to the reference's DecisionTreeRegressor on these inputs (sum_tree, no sklearn)."""
+        try:
+            from AccessMath.preprocessing.content import sum_tree
+        except ImportError:             # this file loaded on its own, by path
+            import importlib.util
+            import os
+            spec = importlib.util.spec_from_file_location("lm_dropin_sum_tree", os.path.join(os.path.dirname(os.path.abspath(__file__)), "sum_tree.py"))
+            sum_tree = importlib.util.module_from_spec(spec)
+            spec.loader.exec_module(sum_tree)
+        return sum_tree.fit(all_sums, leaf_min)
+
+    @staticmethod
+    def get_tree_decision_boundaries(regressor_tree, max_x):
+        """(first frame, predicted value) of every stretch of frames 0 .. max_x - 1 with one predicted value (:43-55)"""
+        predicted = regressor_tree.predict(np.arange(0, max_x, dtype=np.int32).reshape(max_x, 1))
+        changes = np.flatnonzero(predicted[1:] != predicted[:-1]) + 1
+        interval_idxs = [0] + [int(i) for i in changes]
+        return interval_idxs, [predicted[i] for i in interval_idxs]
+
+    @staticmethod
+    def identify_descend_intervals(interval_vals, min_pixels_erased):
+        """Maximal runs (first, last) of stretches each lower than the one before, kept when the value falls by at least
+        min_pixels_erased from the stretch before the run to the run's last (:58-86)."""
+        n = len(interval_vals)
+        falls = [k for k in range(1, n) if interval_vals[k] < interval_vals[k - 1]]
+        runs = []
+        for k in falls:
+            if runs and runs[-1][1] == k - 1:
+                runs[-1][1] = k
+            else:
+                runs.append([k, k])
+        kept = []
+        for first, last in runs:
+            diff = interval_vals[first - 1] - interval_vals[last]
+            ratio = interval_vals[last] / interval_vals[first - 1]         # unused (the ratio test is commented out at :81), but the
+            if diff >= min_pixels_erased:                                   # reference divides: a zero before the run warns or raises
+                kept.append((first, last))
+        return kept
+
+    @staticmethod
+    def video_segments_from_erasing_intervals(erasing_intervals, n_images):
+        """The stretches between the erasures (:89-99).  An erasure that starts at frame 0 leaves a first segment ending at -1; what
+        follows the last erasure counts when it holds more than one frame."""
+        segments, current_start = [], 0
+        for start_erase, end_erase in erasing_intervals:
+            segments.append((current_start, start_erase - 1))
+            current_start = end_erase + 1
+        if current_start < n_images - 1:
+            segments.append((current_start, n_images - 1))
+        return segments
+
+    @staticmethod
+    def video_segments_from_sums(all_sums, min_points, min_erase):
+        """Method 1 (:102-130): fit the tree, take its falling runs that erase at least min_erase of the mean sum, and cut the video
+        from each run's first frame to the first frame of the stretch after it (the last frame when there is none)."""
+        min_pixels_erased = np.array(all_sums).mean() * min_erase
+        regressor = VideoSegmenter.create_regresor_from_sums(all_sums, min_points)
+        interval_idxs, interval_vals = VideoSegmenter.get_tree_decision_boundaries(regressor, len(all_sums))
+        erasing = []
+        for first, last in VideoSegmenter.identify_descend_intervals(interval_vals, min_pixels_erased):
+            last_x = interval_idxs[last + 1] if last + 1 < len(interval_idxs) else len(all_sums) - 1
+            erasing.append((interval_idxs[first], last_x))
+        return VideoSegmenter.video_segments_from_erasing_intervals(erasing, len(all_sums))
 
     @staticmethod
     def _split_conflicts(pairs, start_frame, end_frame, min_conflicts, min_segment_split, min_segment_len, current_depth, graph_data,

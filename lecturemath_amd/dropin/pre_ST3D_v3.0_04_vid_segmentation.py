@@ -2,8 +2,11 @@
 pre_ST3D_v3.0_04_vid_segmentation.py) for VIDEO_SEGMENTATION_METHOD = 3 (deletion events, :44-99; the shipped configuration):
 [(frame_times, frame_indices, compressed_frames), (group_ages, conflicts), SpaceTimeStruct] -> list of (first, last) frame
 intervals; and for method 2 (conflict minimisation, :114-159): [(frame_times, frame_indices, compressed_frames), (group_ages,
-conflicts)] -> the same.  Method 1 (sums + decision tree) is not built.  The reference's debug plots (matplotlib, :100-112, :175-218) and the decompression + sums that only feed them
-(:28-41) are not produced; pass the parameter `sums=1` to get the binary sums printed."""
+conflicts)] -> the same; and for method 1 (sums + regression tree, :160-171): (frame_times, frame_indices, compressed_frames) itself -> the
+same.  The reference's debug plots (matplotlib, :100-112, :175-218) are not produced, nor, for methods 2 and 3, the decompression + sums
+that only feed them (:28-41); pass the parameter `sums=1` to get the binary sums printed.  With LM_PNG_CODEC=device the sums (method 1,
+`sums=1`) are taken on the device: the PNG list is decoded 64 files at a time into device memory and summed there (lm_frame_sums)."""
+import math
 import sys
 import time
 
@@ -64,18 +67,52 @@ def conflict_intervals(process, n_frames, compressed_frames, group_ages, conflic
                                                weights_pixels, weights_time, None, area_divisor=img_size)
 
 
+def binary_sums(compressed_frames):
+    """VideoSegmenter.compute_binary_sums of the decompressed frames (:28-39).  With LM_PNG_CODEC=device the files are decoded a batch
+    at a time into device memory and summed there; no frame comes back to the host."""
+    from AccessMath.preprocessing.content.video_segmenter import VideoSegmenter
+    from lecturemath_amd import png_device
+    if png_device.codec() == "device" and len(compressed_frames):
+        w, h = png_device.png_size(compressed_frames[0])
+        all_sums = []
+        for b0 in range(0, len(compressed_frames), png_device.BATCH):
+            all_sums.extend(VideoSegmenter.compute_binary_sums(png_device.decode_gray8_device(compressed_frames[b0:b0 + png_device.BATCH], w, h)))
+        return all_sums
+    from AccessMath.preprocessing.content.helper import Helper
+    return VideoSegmenter.compute_binary_sums(Helper.decompress_binary_images(compressed_frames))
+
+
+def sums_intervals(process, all_sums):
+    """Method 1 on the frames' sums (:160-171): the reference's keys, read as it reads them (a missing key is 0 and the tree refuses a minimum leaf of 0,
+    as sklearn does there), the minimum leaf of the regression tree in frames, and what it prints."""
+    from AccessMath.preprocessing.content.video_segmenter import VideoSegmenter
+    sampling_fps = process.configuration.get_float("SAMPLING_FPS")
+    sum_min_segment = process.configuration.get_int("VIDEO_SEGMENTATION_SUM_MIN_SEGMENT")
+    sum_min_erase_ratio = process.configuration.get_float("VIDEO_SEGMENTATION_SUM_MIN_ERASE_RATIO")
+    leaf_min = int(math.ceil(sum_min_segment * sampling_fps))
+    intervals = VideoSegmenter.video_segments_from_sums(all_sums, leaf_min, sum_min_erase_ratio)
+    print("Erasing Events: ")
+    print(intervals)
+    print("Total intervals: " + str(len(intervals)))
+    return intervals
+
+
 def process_input(process, input_data):
     from AccessMath.data.space_time_struct import SpaceTimeStruct
     from AccessMath.preprocessing.content.video_segmenter import VideoSegmenter
     segmentation_method = process.configuration.get_int("VIDEO_SEGMENTATION_METHOD", 3)
-    if segmentation_method not in (2, 3):
-        raise NotImplementedError("VIDEO_SEGMENTATION_METHOD = %d is not built: 3 (deletion events, the shipped configuration) and "
-                                  "2 (conflict minimisation) are" % segmentation_method)
+    if segmentation_method not in (1, 2, 3):
+        raise NotImplementedError("VIDEO_SEGMENTATION_METHOD = %d is not built: 3 (deletion events, the shipped configuration), "
+                                  "2 (conflict minimisation) and 1 (sums) are" % segmentation_method)
+    if segmentation_method == 1:
+        frame_times, frame_indices, compressed_frames = input_data
+        print("Decompressing input...")
+        print("Computing sums...")
+        return sums_intervals(process, binary_sums(compressed_frames))
     frame_times, frame_indices, compressed_frames = input_data[0]
     if "sums" in process.params:
-        from AccessMath.preprocessing.content.helper import Helper
         print("Computing sums...")
-        print(VideoSegmenter.compute_binary_sums(Helper.decompress_binary_images(compressed_frames)))
+        print(binary_sums(compressed_frames))
     group_ages, conflicts = input_data[1]
     if segmentation_method == 2:
         intervals = conflict_intervals(process, len(frame_indices), compressed_frames, group_ages, conflicts,

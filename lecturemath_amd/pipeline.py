@@ -10,7 +10,8 @@ the device unless asked for).
 
 The stages are the drop-in classes and scripts themselves (lecturemath_amd/dropin: CCStabilityEstimator,
 pre_ST3D_v3.0_03/04/05 process_input), so every product is the one the step-by-step scripts give; only the hand-offs differ
-(add_frames_device / no PNG).  `out` holds: group_ages, conflicts, st3d (SpaceTimeStruct), intervals, keyframes, cc_times,
+(add_frames_device / no PNG; with VIDEO_SEGMENTATION_METHOD = 1 step 04 gets the sums of the reconstructed frames from the device,
+CCStabilityEstimator.reconstructed_frame_sums, instead of the frames).  `out` holds: group_ages, conflicts, st3d (SpaceTimeStruct), intervals, keyframes, cc_times,
 and -- lazily, on request -- the reconstructed frames as PNG byte strings like the reference's CC_RECONSTRUCTED_OUTPUT
 (finish(reconstructed_png=True): host zlib; "device": encoded on the device, lecturemath_amd.png_device).
 finish(keyframes="device") keeps step 05 on the device as well: the group images stay the bit rows step 03 wrote, `out` gains
@@ -31,6 +32,7 @@ DEFAULT_CONF = {   # the shipped values (configs/FCN_LectureNet.conf), as the sc
     "VIDEO_SEGMENTATION_METHOD": "3", "VIDEO_SEGMENTATION_DEL_EVENT_ADD_THRESHOLD": "10",
     "VIDEO_SEGMENTATION_DEL_EVENT_MIN_LENGTH": "15", "VIDEO_SEGMENTATION_DEL_EVENT_THRESHOLD": "0.25",
     "FCN_BINARIZER_BINARY_THRESHOLD": "128",
+    "SAMPLING_FPS": "1.0", "VIDEO_SEGMENTATION_SUM_MIN_SEGMENT": "10", "VIDEO_SEGMENTATION_SUM_MIN_ERASE_RATIO": "0.05",
 }
 
 
@@ -139,7 +141,12 @@ class LecturePipeline:
         import io
         sink = contextlib.nullcontext() if self.verbose else contextlib.redirect_stdout(io.StringIO())
         with sink:
-            intervals = _script("pre_ST3D_v3.0_04_vid_segmentation.py").process_input(self.process, step03)
+            step04 = _script("pre_ST3D_v3.0_04_vid_segmentation.py")
+            if cfg.get_int("VIDEO_SEGMENTATION_METHOD", 3) == 1:
+                # the sums of the reconstructed frames straight from the group images: no frame is rendered, no PNG written or read
+                intervals = step04.sums_intervals(self.process, [int(v) / 255 for v in est.reconstructed_frame_sums()])
+            else:
+                intervals = step04.process_input(self.process, step03)
             (summary_indices, summary_times, summary_keyframes), = _script("pre_ST3D_v3.0_05_generate_summary.py").process_input(self.process, [st3d, intervals])
         from AccessMath.preprocessing.content.keyframe_extractor import KeyframeExtractor   # noqa: F401  (cc_times below)
         return {"group_ages": group_ages, "conflicts": conflicts, "st3d": st3d, "intervals": intervals, "keyframes": summary_keyframes,
