@@ -287,6 +287,28 @@ int lm_kf_image(LmKeyframes* kf, int item, uint8_t* h_out, int64_t bytes, void* 
  * rest on the crowded-tile path, since the handle was created. */
 int lm_kf_crowded_tiles(LmKeyframes* kf, int64_t* h_count, void* stream);
 
+/* ---- translation alignment of binary images (csrc/lm_align.hip) ------------------------------------------------------------
+ * Aligner.computeTranslationAlignment (AccessMath/preprocessing/content/aligner.py:27-83), the first stage of the reference's
+ * summary evaluation (Evaluator.keyframes_alignments, Evaluator.parallel_keyframe_align): for a pair of width x height images and
+ * every displacement (dy, dx) in [-w, w]^2 the number of pixels that are ink in the first image at (y, x) and in the second at
+ * (y - dy, x - dx).  The handle holds up to max_images images as bit rows and answers for a list of pairs per call; its scratch
+ * grows on demand and is kept, so a repeated call of the same size allocates nothing.
+ * Limits: width, height <= 32768 (so every count fits int32); window <= 128 (LM_ALIGN_MAX_WINDOW), <= the max_window the
+ * handle was created with, and <= min(width, height) (beyond which the reference itself raises). */
+typedef struct LmAlign LmAlign;
+LmAlign* lm_align_create(int width, int height, int max_images, int max_window, void* stream);
+void lm_align_destroy(LmAlign* al);
+/* n_images (<= max_images, else LM_ERR_CAPACITY) images replace the handle's: image i, pixel (y, x) is the byte at
+ * images[((i * height + y) * width + x) * pixel_stride] (pixel_stride >= 1: 3 reads channel 0 of [n][H][W][3] in place), ink
+ * where it equals content_lum; any other value is "not ink".  on_device: `images` is device memory (asynchronous on `stream`);
+ * else host memory, read when the call returns.  n_images == 0 succeeds and leaves the handle empty. */
+int lm_align_set_images(LmAlign* al, const uint8_t* images, int on_device, int n_images, int64_t pixel_stride, int content_lum, void* stream);
+/* ink pixels of every image, h_totals [n_images] (HOST).  Synchronises `stream`. */
+int lm_align_totals(LmAlign* al, int64_t* h_totals, void* stream);
+/* h_pairs [n_pairs][2] image indices (first, second; HOST) -> h_matches [n_pairs][2w + 1][2w + 1] (HOST), dy-major:
+ * h_matches[p][dy + w][dx + w] with w = max_window.  n_pairs == 0 succeeds and writes nothing.  Synchronises `stream`. */
+int lm_align_run(LmAlign* al, const int32_t* h_pairs, int n_pairs, int max_window, int32_t* h_matches, void* stream);
+
 /* ---- the remaining exports of the reference's accessmath_lib.c (classical, pre-FCN binarizers) --------
  * Same symbols and C signatures as the reference, host pointers (ctypes), results bit-identical to the C library:
  *   accessmath_lib.c:7-111    speaker_detection_handle_frame (bound by AccessMath/preprocessing/video_worker/ speaker detection)

@@ -1425,3 +1425,4 @@ extern "C" int lm_stream_import_assign(LmStream* s, const void* d_in, int64_t by
 #include "lm_png.hip"
 #include "lm_segment.hip"
 #include "lm_keyframes.hip"
+#include "lm_align.hip"
