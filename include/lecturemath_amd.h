@@ -287,6 +287,21 @@ int lm_kf_image(LmKeyframes* kf, int item, uint8_t* h_out, int64_t bytes, void* 
  * rest on the crowded-tile path, since the handle was created. */
 int lm_kf_crowded_tiles(LmKeyframes* kf, int64_t* h_count, void* stream);
 
+/* Shared ink of pairs of items under a displacement (csrc/lm_ccmatch.hip): the integer primitive of the reference's summary
+ * evaluation (AccessMath/evaluation/evaluator.py: check_equivalent_cc, keyframes_overlapping_ccs, match_overlapping_ccs,
+ * find_ccs_overlapping_background).  Query q names list A = h_a_items[h_a_off[q] .. h_a_off[q + 1]), list B likewise, and
+ * h_disp[q] = (dy, dx), applied to every item of B.  A row (query, position in A, position in B) is written to h_rows [cap][3],
+ * sorted by all three, for every pair whose boxes touch (the inclusive test of ConnectedComponent.getOverlapFMeasure) for at least
+ * one extra displacement (ey, ex) in [-radius, radius]^2; rows whose counts are all zero are kept.  h_counts [cap][2r + 1][2r + 1],
+ * ey-major: counts[ey + r][ex + r] = number of (y, x) with ink of the A item at (y, x) and ink of the B item at (y - dy - ey,
+ * x - dx - ex), in frame coordinates that are not clipped to the frame.
+ * Limits (LM_ERR_ARG): radius <= 8; |dy|, |dx| <= 32768; every item inside the table.  *n_found = rows found; LM_ERR_CAPACITY when
+ * that exceeds cap (nothing is written then).  n_q == 0 and empty lists succeed.  All pointers HOST.  Two stream synchronisations;
+ * the scratch is kept on the handle and only grows, so a repeated call of the same size allocates nothing. */
+int lm_kf_pair_counts(LmKeyframes* kf, const int64_t* h_a_off, const int32_t* h_a_items, const int64_t* h_b_off,
+                      const int32_t* h_b_items, const int32_t* h_disp, int n_q, int radius, int32_t* h_rows, int32_t* h_counts,
+                      int64_t cap, int64_t* n_found, void* stream);
+
 /* ---- translation alignment of binary images (csrc/lm_align.hip) ------------------------------------------------------------
  * Aligner.computeTranslationAlignment (AccessMath/preprocessing/content/aligner.py:27-83), the first stage of the reference's
  * summary evaluation (Evaluator.keyframes_alignments, Evaluator.parallel_keyframe_align): for a pair of width x height images and

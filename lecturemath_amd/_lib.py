@@ -112,6 +112,7 @@ SIGNATURES = {
     "lm_kf_render": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
     "lm_kf_image": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _i64, _vp]),
     "lm_kf_crowded_tiles": (ctypes.c_int, [_vp, _vp, _vp]),
+    "lm_kf_pair_counts": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _i64, _vp, _vp]),
     "lm_align_create": (_vp, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
     "lm_align_destroy": (None, [_vp]),
     "lm_align_set_images": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_int, _vp]),

@@ -175,9 +175,9 @@ struct LmKeyframes {
     const uint32_t* d_bits = nullptr;           // the group's d_gbits (view) or d_owned
     uint32_t* d_owned = nullptr;
     unsigned long long* d_crowded = nullptr;    // tiles that took the crowded-tile path, since creation
-    void* ws[4] = {nullptr, nullptr, nullptr, nullptr};     // grow-only scratch: join, bit tests, render, image
-    size_t ws_cap[4] = {0, 0, 0, 0};
-    std::vector<char> stage[4];                 // host side of the uploads (alive until the next call)
+    void* ws[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // grow-only scratch: join, bit tests, render, image,
+    size_t ws_cap[6] = {0, 0, 0, 0, 0, 0};                                  // and the two of lm_kf_pair_counts (lm_ccmatch.hip)
+    std::vector<char> stage[6];                 // host side of the uploads (alive until the next call)
 };
 
 static void* lm_kf_scratch(LmKeyframes* kf, int slot, size_t bytes, const char* who)

@@ -437,6 +437,102 @@ class TranslationAligner:
         return [self.best_alignment(counts[k], totals[i], totals[j], sort_by) for k, (i, j) in enumerate(pairs)]
 
 
+CC_PAIR_MAX_RADIUS = 8      # LM_CCM_MAX_RADIUS of csrc/lm_ccmatch.hip
+
+
+class CCPairCounts:
+    """Shared ink of pairs of connected components under a displacement (lm_kf_pair_counts in include/lecturemath_amd.h): the
+    integer primitive of the reference's summary evaluation (AccessMath/evaluation/evaluator.py).
+
+    CCPairCounts(cc_lists, width, height)   cc_lists: one list per keyframe of objects with min_x, max_x, min_y, max_y and img
+                                            (ConnectedComponent) or of (box, img) tuples, box = (min_x, max_x, min_y, max_y); all of
+                                            them become items of one bit-row table, uploaded once.  `extra` appends full images such
+                                            as an object mask: (box, img) tuples that form one more list.
+    item(k, i)                              table item of element i of list k
+    counts(queries, radius)                 queries: (items of A, items of B, (dy, dx)) -> rows int32 [n][3] = (query, position in
+                                            A, position in B), sorted, and counts int64 [n][2r + 1][2r + 1], [ey + r][ex + r]"""
+
+    def __init__(self, cc_lists, width, height, extra=(), lib=None):
+        self.lib = lib or _lib.load()
+        self.be = Backend(self.lib)
+        self.width, self.height = int(width), int(height)
+        lists = [list(lst) for lst in cc_lists] + [list(extra)]
+        self.list_off = np.zeros(len(lists) + 1, np.int64)
+        self.list_off[1:] = np.cumsum([len(lst) for lst in lists])
+        boxes, images = [], []
+        for lst in lists:
+            for cc in lst:
+                box, img = cc if isinstance(cc, tuple) else ((cc.min_x, cc.max_x, cc.min_y, cc.max_y), cc.img)
+                boxes.append([int(v) for v in box])
+                images.append(np.asarray(img))
+        n = len(images)
+        hb = np.ascontiguousarray(np.asarray(boxes, np.int32).reshape(n, 4))
+        off = np.zeros(n + 1, np.int64)
+        off[1:] = np.cumsum([im.size for im in images])
+        flat = np.ascontiguousarray(np.concatenate([(im != 0).astype(np.uint8).ravel() for im in images])) if n else np.zeros(1, np.uint8)
+        self.handle = self.lib.lm_kf_create_from_images(hb.ctypes.data if n else None, flat.ctypes.data if n else None,
+                                                        off.ctypes.data if n else None, n, self.width, self.height, self.be.stream())
+        if not self.handle:
+            raise _lib.LecturemathError(_lib.LM_ERR_ARG, self.lib.last_error())
+        self.n_items = n
+        self.calls = 0              # lm_kf_pair_counts calls made (tests assert that cached results launch nothing)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.lm_kf_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __reduce__(self):
+        raise TypeError("CCPairCounts is a handle to device memory and cannot be pickled")
+
+    def _live(self):
+        if getattr(self, "handle", None) is None:
+            raise ValueError("CCPairCounts: the handle is closed")
+        return self.handle
+
+    def item(self, k, i):
+        return int(self.list_off[k]) + int(i)
+
+    def items(self, k):
+        """the items of list k (k = -1: the extra list)"""
+        k = k % (len(self.list_off) - 1)
+        return np.arange(self.list_off[k], self.list_off[k + 1], dtype=np.int32)
+
+    def counts(self, queries, radius, cap=None):
+        handle = self._live()
+        queries = list(queries)
+        n_q, r = len(queries), int(radius)
+        a_off, a_items = GroupImages._csr([q[0] for q in queries])
+        b_off, b_items = GroupImages._csr([q[1] for q in queries])
+        disp = np.ascontiguousarray(np.asarray([q[2] for q in queries], np.int64).reshape(n_q, 2))
+        if n_q and np.abs(disp).max() > 0x7fffffff:
+            raise ValueError("CCPairCounts.counts: displacement beyond int32")
+        disp = np.ascontiguousarray(disp.astype(np.int32))
+        side = 2 * max(r, 0) + 1
+        cap = int(cap) if cap is not None else max(1024, 4 * int(a_off[-1] + b_off[-1]))
+        for attempt in range(2):
+            rows = np.zeros((cap, 3), np.int32)
+            counts = np.zeros((cap, side, side), np.int32)
+            found = np.zeros(1, np.int64)
+            self.calls += 1
+            rc = self.lib.lm_kf_pair_counts(handle, a_off.ctypes.data, a_items.ctypes.data, b_off.ctypes.data, b_items.ctypes.data,
+                                            disp.ctypes.data if n_q else None, n_q, r, rows.ctypes.data, counts.ctypes.data, cap,
+                                            found.ctypes.data, self.be.stream())
+            if rc == _lib.LM_ERR_CAPACITY and int(found[0]) > cap and attempt == 0:
+                cap = int(found[0])         # the retry gets the exact room
+                continue
+            self.lib.check(rc)
+            break
+        n = int(found[0])
+        return rows[:n].copy(), counts[:n].astype(np.int64)
+
+
 class _LazyImageList:
     """cc_group_images[g]: len() and [k] backed by GroupImages.image, nothing held"""
 

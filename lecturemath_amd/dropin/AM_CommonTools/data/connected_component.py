@@ -65,6 +65,15 @@ class ConnectedComponent:
             return (2.0 * match) / float(self.size + other.size)
         return match / float(self.size), match / float(other.size)
 
+    def strID(self):
+        return "%d-%d-%d-%d-%d" % (self.min_x, self.max_x, self.min_y, self.max_y, self.size)
+
+    def translateBox(self, disp_x, disp_y):
+        self.min_x += disp_x
+        self.max_x += disp_x
+        self.min_y += disp_y
+        self.max_y += disp_y
+
     def __str__(self):
         return "ConnectedComponent -> Id = %s\n -> X : [%s, %s] \n -> Y : [%s, %s]" % (
             self.cc_id, self.min_x, self.max_x, self.min_y, self.max_y)
