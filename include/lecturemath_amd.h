@@ -152,7 +152,15 @@ int lm_stream_run_logits(LmStream* s, const float* d_logits, int n_frames, int b
  * per-lecture pickles as the hand-off between the per-frame half (labeler.py:116-191) and add_frame's matching
  * (cc_stability_estimator.py:71-145).  lm_stream_pack_size synchronises and returns the bytes lm_stream_pack will write;
  * lm_stream_append_packed appends a packed block behind the last frame of `s` (frame numbers and crop offsets are rebased on
- * the device); the appended frames are unmatched until lm_stream_match. */
+ * the device); the appended frames are unmatched until lm_stream_match.
+ * Block layout (little endian; every byte is written, equal frame ranges of equal streams give equal bytes):
+ *   int64 {n_frames, n_cc, n_words, 0x4c4d504b31 "LMPK1"}
+ *   int64 kept-CC count of each frame, padded with ZERO entries to a multiple of four entries
+ *   n_cc records of 32 bytes: int32 cc_id, size; int16 min_x, max_x, min_y, max_y; uint64 crop_off (relative to the block's
+ *     first crop word); int32 frame (relative to first_frame), pad = 0
+ *   n_words uint32 crop words
+ * lm_stream_append_packed returns LM_ERR_ARG for a buffer that is misaligned, carries another magic or is shorter than its
+ * header says, and LM_ERR_CAPACITY when `s` cannot hold the block; a refused block leaves `s` as it was. */
 int lm_stream_pack_size(LmStream* s, int first_frame, int n_frames, int64_t* h_bytes, void* stream);
 int lm_stream_pack(LmStream* s, int first_frame, int n_frames, void* d_buf, int64_t bytes, void* stream);
 int lm_stream_append_packed(LmStream* s, const void* d_buf, int64_t bytes, void* stream);
@@ -161,7 +169,11 @@ int lm_stream_append_packed(LmStream* s, const void* d_buf, int64_t bytes, void*
  * cc_stability_estimator.py:102,117) + {n_cc, n_unique, tempo_count, n_frames} as one flat DEVICE buffer of
  * lm_stream_assign_bytes() bytes (32-byte aligned).  The receiver appends the packed block(s) of the same frames first
  * (lm_stream_append_packed), then imports the assignment: the stream is then what the sender's was after matching, as far as
- * lm_group_run reads it (the active list stays behind: step 03 does not use it). */
+ * lm_group_run reads it (the active list stays behind: step 03 does not use it).
+ * Buffer layout (little endian; every byte is written): int32 assign[n_cc]; zero bytes up to the next multiple of 32; int64
+ * {n_cc, n_unique, tempo_count, n_frames}.  lm_stream_export_assign wants exactly lm_stream_assign_bytes() bytes (LM_ERR_ARG
+ * otherwise) and a fully matched stream (LM_ERR_STATE); lm_stream_import_assign returns LM_ERR_ARG for an assignment whose
+ * n_cc / n_frames are not those of `s`. */
 int lm_stream_assign_bytes(LmStream* s, int64_t* bytes, void* stream);
 int lm_stream_export_assign(LmStream* s, void* d_out, int64_t bytes, void* stream);
 int lm_stream_import_assign(LmStream* s, const void* d_in, int64_t bytes, void* stream);

@@ -1192,9 +1192,11 @@ extern "C" int lm_stream_read(LmStream* s, int32_t* h_rec, int64_t* h_frame_off,
 // ------------------------------------------------------------------------------------------------
 // Frame-range sharding: the CC records + crops of whole frames as ONE flat device buffer, so that the gather to
 // the rank that replays the temporal matching is one send / recv per rank over RCCL (no pickling, no host copy).
-// Layout (bytes): [0,32) header int64 {n_frames, n_cc, n_words, magic}; int64 kept-CC counts per frame, padded to a multiple
-// of four entries; the 32-byte LmCcRec records (frame numbers relative to the block's first frame, crop offsets relative to
-// its first crop word); the uint32 crop words.
+// Layout (bytes, little endian): [0,32) header int64 {n_frames, n_cc, n_words, magic}; int64 kept-CC counts per frame, padded
+// to a multiple of four entries -- the padding entries are zero; the 32-byte LmCcRec records {int32 cc_id, size; int16 min_x,
+// max_x, min_y, max_y; uint64 crop_off; int32 frame, pad} (frame numbers relative to the block's first frame, crop offsets
+// relative to its first crop word); the uint32 crop words.  lm_stream_pack writes every byte of the block: equal frame ranges of
+// equal streams give equal bytes.
 // ------------------------------------------------------------------------------------------------
 #define LM_PACK_MAGIC 0x4c4d504b31ll   /* "LMPK1" */
 
@@ -1211,7 +1213,8 @@ __global__ void __launch_bounds__(256) lm_k_pack_block(const LmCcRec* __restrict
 {
     const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long long)gridDim.x * blockDim.x;
     if (tid == 0) { head[0] = n_frames; head[1] = n_cc; head[2] = nw; head[3] = LM_PACK_MAGIC; }
-    for (long long i = tid; i < n_frames; i += nth) head[4 + i] = frame_cc_off[first + i + 1] - frame_cc_off[first + i];
+    const long long n_counts = ((long long)n_frames + 3) & ~3ll;        // the padding entries are written too (zero): every byte of a block is defined
+    for (long long i = tid; i < n_counts; i += nth) head[4 + i] = (i < n_frames) ? frame_cc_off[first + i + 1] - frame_cc_off[first + i] : 0ll;
     for (long long i = tid; i < n_cc; i += nth) {
         LmCcRec r = cc[c0 + i];
         r.frame -= first;
@@ -1361,7 +1364,8 @@ extern "C" int lm_stream_append_packed(LmStream* s, const void* d_buf, int64_t b
 
 // Hand-off of a MATCHED stream to another rank (step 03 on a rank of its own): the packed block carries records and crops, this
 // carries what the temporal matching added -- the unique index of every kept CC (cc_idx_per_frame, cc_stability_estimator.py:102,117)
-// and the counters.  d_out: int32 [n_cc] + 4 x int64 {n_cc, n_unique, tempo_count, n_frames} (d_out must hold lm_stream_assign_bytes).
+// and the counters.  Layout of d_out (bytes, little endian): int32 assign[n_cc]; zero bytes up to the next multiple of 32; 4 x int64
+// {n_cc, n_unique, tempo_count, n_frames}.  `bytes` must be what lm_stream_assign_bytes returned; every byte is written.
 __global__ void __launch_bounds__(256) lm_k_assign_tail(const LmCounters* __restrict__ cnt, long long* __restrict__ tail)
 {
     if (threadIdx.x == 0) { tail[0] = cnt->n_cc; tail[1] = cnt->n_uniq; tail[2] = (long long)cnt->tempo_count; tail[3] = cnt->n_matched; }
@@ -1390,9 +1394,18 @@ extern "C" int lm_stream_export_assign(LmStream* s, void* d_out, int64_t bytes, 
     if (!s || !d_out || bytes < 32 || (((uintptr_t)d_out) & 31)) { lm_set_error("lm_stream_export_assign: bad arguments"); return LM_ERR_ARG; }
     if (s->frames_matched != s->frames_pushed) { lm_set_error("lm_stream_export_assign: %d frames are unmatched", s->frames_pushed - s->frames_matched); return LM_ERR_STATE; }
     hipStream_t st = (hipStream_t)stream;
-    const long long n_cc = (long long)((bytes - 32) / 4);       // the caller sized the buffer with lm_stream_assign_bytes
-    LM_HIP(hipMemcpyAsync(d_out, s->assign, (size_t)(bytes - 32), hipMemcpyDeviceToDevice, st));
-    (void)n_cc;
+    LmCounters h;
+    LM_HIP(hipMemcpyAsync(&h, s->counters, sizeof(h), hipMemcpyDeviceToHost, st));
+    LM_HIP(hipStreamSynchronize(st));
+    if (h.error) { lm_set_error("lm_stream_export_assign: stream capacity exceeded on device"); return h.error; }
+    if ((size_t)bytes != lm_assign_bytes(h.n_cc)) {             // the caller sizes the buffer with lm_stream_assign_bytes
+        lm_set_error("lm_stream_export_assign: buffer of %lld bytes, the stream's %lld CCs need %lld", (long long)bytes, h.n_cc, (long long)lm_assign_bytes(h.n_cc));
+        return LM_ERR_ARG;
+    }
+    // exactly the stream's n_cc entries: what lies behind them in assign[] belongs to an earlier stream of this handle (or to nobody)
+    const size_t used = (size_t)h.n_cc * 4, pad = (size_t)bytes - 32 - used;
+    if (used) LM_HIP(hipMemcpyAsync(d_out, s->assign, used, hipMemcpyDeviceToDevice, st));
+    if (pad) LM_HIP(hipMemsetAsync((char*)d_out + used, 0, pad, st));
     hipLaunchKernelGGL(lm_k_assign_tail, dim3(1), dim3(64), 0, st, s->counters, (long long*)((char*)d_out + bytes - 32));
     LM_HIP(hipGetLastError());
     return LM_OK;
