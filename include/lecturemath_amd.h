@@ -213,7 +213,9 @@ typedef struct LmGroups LmGroups;
  * compute_overlapping_stable_cc(t_window), compute_groups(min_recall), compute_groups_temporal_information,
  * compute_conflicting_groups, compute_group_images(img_threshold) and prepares frames_from_groups when
  * reconstruct_tables != 0.  Box join, pixel overlaps, group images and frame rendering run on the device;
- * the order-dependent list bookkeeping runs on the host.  Returns NULL on failure (lm_last_error). */
+ * the order-dependent list bookkeeping runs on the host.  Returns NULL on failure (lm_last_error).
+ * A NaN min_recall or img_threshold is refused (NULL).  An img_threshold above 1 -- +inf included -- gives empty group images
+ * and one below 0 what 0 gives (every pixel of every box), as in the reference; neither value reaches a kernel as it is. */
 LmGroups* lm_group_run(LmStream* s, int max_gap, int min_times, int t_window, double min_recall, double img_threshold,
                        int reconstruct_tables, void* stream);
 void lm_group_destroy(LmGroups* g);

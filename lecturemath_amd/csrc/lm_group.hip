@@ -1839,6 +1839,16 @@ extern "C" LmGroups* lm_group_run(LmStream* s, int max_gap, int min_times, int t
                                   int reconstruct_tables, void* stream)
 {
     if (!s) { lm_set_error("lm_group_run: null stream"); return nullptr; }
+    // the thresholds reach kernels as they are, so they are checked here, before any launch.  NaN has no device counterpart: numpy's
+    // (mask / max >= nan) clears every pixel and the reference's (recall < nan) keeps every edge, the device comparisons do the opposite.
+    if (min_recall != min_recall || img_threshold != img_threshold) {
+        lm_set_error("lm_group_run: min_recall / img_threshold is NaN");
+        return nullptr;
+    }
+    // v <= max, so no pixel passes a threshold above 1: every such value (+inf, 1e300) gives the reference's empty images, and the integer
+    // bound of lm_gimg_vmin / lm_gimg_write_tile ((int)(thr * mx), then a loop up to thr) is only defined for a threshold of this size.
+    if (img_threshold > 1.0) img_threshold = 2.0;
+    if (img_threshold < 0.0) img_threshold = 0.0;       // v >= 0: every pixel passes, as at 0 (and -inf * mx has no integer either)
     LmGroups* g = new LmGroups();
     g->s = s;
     if (!s->garena_busy) {
