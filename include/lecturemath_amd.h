@@ -338,6 +338,46 @@ int lm_align_totals(LmAlign* al, int64_t* h_totals, void* stream);
  * h_matches[p][dy + w][dx + w] with w = max_window.  n_pairs == 0 succeeds and writes nothing.  Synchronises `stream`. */
 int lm_align_run(LmAlign* al, const int32_t* h_pairs, int n_pairs, int max_window, int32_t* h_matches, void* stream);
 
+/* ---- pixel history of a binary stream (csrc/lm_history.hip) ----------------------------------------------------------------
+ * For every pixel: in how many frames of a frame range was it ink, and when first?  The integer core of
+ * CCStabilityEstimator.compute_group_images_from_raw_binary (cc_stability_estimator.py:502-573) and KeyframeExtractor.extract
+ * (keyframe_extractor.py:146-222).  The handle holds up to max_frames frames of width x height (both <= 32768) as bit rows:
+ * ceil(width / 32) 32-bit words per row, frame after frame, bit = ink (an LmKeyframes item at x0 = y0 = 0 per frame);
+ * max_frames * height * ceil(width / 32) * 4 bytes of device memory, allocated by lm_hist_create.
+ * Limit: a frame range [t0, t1] (inclusive) holds at most 65,535 frames (16 bit-sliced counter planes), else LM_ERR_ARG. */
+typedef struct LmHistory LmHistory;
+LmHistory* lm_hist_create(int width, int height, int max_frames);
+void lm_hist_destroy(LmHistory* h);
+/* frames held (-1 for NULL) */
+int lm_hist_count(const LmHistory* h);
+/* d_frames: device uint8 [n][height][width], 255 = ink, 0 = none; packed on the device and appended.  A byte that is neither 0 nor
+ * 255 gives LM_ERR_ARG (the reference's `bitwise_and(frame, mask) // 255` and `frame / 255` give such bytes a meaning of their own
+ * that is not reproduced), more frames than max_frames LM_ERR_CAPACITY; the history is then as it was.  The ink pixels of every
+ * frame are counted in the same pass.  Synchronises `stream`. */
+int lm_hist_append(LmHistory* h, const uint8_t* d_frames, int n, void* stream);
+/* forgets the frames from n_frames on (0 <= n_frames <= count) */
+int lm_hist_truncate(LmHistory* h, int n_frames);
+/* ink pixels of frames first .. first + n - 1, h_counts [n] (HOST; kept on the host since the append) */
+int lm_hist_ink_counts(const LmHistory* h, int first, int n, int64_t* h_counts);
+/* the bit rows of frames first .. first + n - 1 to the host: h_words [n][height][ceil(width / 32)].  Synchronises `stream`. */
+int lm_hist_read_bits(const LmHistory* h, int first, int n, uint32_t* h_words, void* stream);
+/* Per pixel over the frames t0 .. t1: d_sum [height][width] = frames with ink, d_age = index of the first frame with ink (0 where
+ * none, as the reference leaves it); both device float32, the reference's dtype (exact: counts <= 65,535, indices < 2^24 or rounded
+ * as numpy rounds them).  Asynchronous on `stream`. */
+int lm_hist_segment_stats(LmHistory* h, int t0, int t1, float* d_sum, float* d_age, void* stream);
+/* Job j: the box h_boxes[j] = (min_x, max_x, min_y, max_y) inclusive, inside the frame; the frames h_ranges[j] = (t0, t1) inclusive;
+ * the mask items h_list_items[h_list_off[j] .. h_list_off[j + 1]) of `masks` (a table placed in the same width x height frame, each
+ * item at its own box).  c(y, x) = number of frames of the range whose pixel is ink and lies under the OR of the job's mask items;
+ * m = max c over the box, written to h_max_out[j] (HOST, may be NULL).  Returns a new table that owns its memory: item j has job j's
+ * box and holds ((c * 255) // m) > threshold -- in integers, with k = floor(threshold) + 1: c * 255 >= k * m, the cut computed on the
+ * host in 64 bits per job; m == 0 (numpy's int32 // 0 yields 0): empty for threshold >= 0, every pixel of the box below.  The counts
+ * are computed twice (maximum, then threshold) unless the cut decides the job alone; no scratch grows with the image area.  NULL
+ * (lm_last_error) on failure: a box outside the frame, a range outside the history or above the limit, a mask item outside its
+ * table, a NaN threshold.  All pointers HOST.  Synchronises `stream`. */
+LmKeyframes* lm_hist_masked_images(LmHistory* h, LmKeyframes* masks, const int32_t* h_boxes, const int32_t* h_ranges,
+                                   const int64_t* h_list_off, const int32_t* h_list_items, int n_jobs, double threshold,
+                                   int64_t* h_max_out, void* stream);
+
 /* ---- the remaining exports of the reference's accessmath_lib.c (classical, pre-FCN binarizers) --------
  * Same symbols and C signatures as the reference, host pointers (ctypes), results bit-identical to the C library:
  *   accessmath_lib.c:7-111    speaker_detection_handle_frame (bound by AccessMath/preprocessing/video_worker/ speaker detection)

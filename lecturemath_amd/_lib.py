@@ -118,6 +118,15 @@ SIGNATURES = {
     "lm_align_set_images": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_int, _vp]),
     "lm_align_totals": (ctypes.c_int, [_vp, _vp, _vp]),
     "lm_align_run": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    "lm_hist_create": (_vp, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "lm_hist_destroy": (None, [_vp]),
+    "lm_hist_count": (ctypes.c_int, [_vp]),
+    "lm_hist_append": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp]),
+    "lm_hist_truncate": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "lm_hist_ink_counts": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
+    "lm_hist_read_bits": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    "lm_hist_segment_stats": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
+    "lm_hist_masked_images": (_vp, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _f64, _vp, _vp]),
 }
 
 

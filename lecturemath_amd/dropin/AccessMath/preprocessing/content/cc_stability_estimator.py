@@ -237,6 +237,83 @@ class CCStabilityEstimator:
         r = self._cur(self._thr).result(with_images=True, with_clean=False)
         return r["group_images"], r["group_boundaries"]
 
+    def _unique_masks(self, used):
+        """({u: box}, {u: img}, {u: (first frame, last frame)}, integer type of the boxes) of the unique CCs `used`.  An estimator
+        whose attributes are set or already materialised answers from them; otherwise the records and crops are read from the device
+        once and only the CCs asked for become images (a lecture holds millions of raw CCs, the groups name a fraction)."""
+        d = self.__dict__
+        if "unique_cc_objects" in d or d.get("_host") is not None or d.get("_imported") is not None or "_stream" not in d:
+            objects, cc_frames = self.unique_cc_objects, self.unique_cc_frames
+            box_of = {c: (int(objects[c].min_x), int(objects[c].max_x), int(objects[c].min_y), int(objects[c].max_y)) for c in used}
+            int_type = type(objects[used[0]].min_x) if used else int
+            return box_of, {c: objects[c].img for c in used}, {c: (cc_frames[c][0][0], cc_frames[c][-1][0]) for c in used}, int_type
+        self._flush()
+        r = self._stream.read(with_crops=True)
+        rec = r["rec"]
+        u = np.asarray(used, np.int64)
+        if self._split is not None:
+            g = self._grouping()
+            off, lst = g.array("ulist_off"), g.array("ulist_cc")
+            rep, first_cc, last_cc = g.array("uniq_cc")[u], lst[off[u]], lst[off[u + 1] - 1]
+        else:
+            order = np.arange(len(rec))
+            first_of, last_of = np.zeros(r["n_unique"], np.int64), np.zeros(r["n_unique"], np.int64)
+            first_of[rec[::-1, 7]] = order[::-1]
+            last_of[rec[:, 7]] = order
+            rep = first_cc = first_of[u]
+            last_cc = last_of[u]
+        box_of, img_of, life = {}, {}, {}
+        for k, c in enumerate(used):
+            mnx, mxx, mny, mxy = (int(v) for v in rec[rep[k], 1:5])
+            nwords = ((mxx >> 5) - (mnx >> 5) + 1) * (mxy - mny + 1)
+            o = int(r["crop_off"][rep[k]])
+            box_of[c] = (mnx, mxx, mny, mxy)
+            img_of[c] = device.decode_crop(r["crop"][o:o + nwords], mnx, mxx, mny, mxy)
+            life[c] = (int(rec[first_cc[k], 6]), int(rec[last_cc[k], 6]))
+        return box_of, img_of, life, np.int32
+
+    def compute_group_images_from_raw_binary(self, cc_groups, group_ages, binary_frames, segment_threshold):
+        """(:502-573) The pixel-voting variant of compute_group_images: per age segment of a group, the ink of the raw binary frames
+        under the union mask of the members alive in the segment, counted per pixel, scaled to 0..255 by the image's maximum and
+        cut at segment_threshold.  Honours the cc_groups and group_ages it is given.  binary_frames: a list of uint8 frames, a
+        device uint8 tensor [n, H, W], or a lecturemath_amd.device.FrameHistory (used as it is).  The frames are bit rows on the
+        device (FrameHistory), the masks the unique CCs uploaded once, the images a table of bit rows: group_images is a
+        LazyGroupImages over it (group_images[g][k] is the reference's uint8 array, expanded on demand) whose device_images is the
+        GroupImages step 05 takes (KeyframeExtractor.GenerateFromGroupImages(gi, gi.item_first, ...)).  An age segment holds at
+        most FrameHistory.MAX_RANGE frames (ValueError)."""
+        n_groups = len(cc_groups)
+        used = sorted({int(c) for group in cc_groups for c in group})
+        slot = {c: i for i, c in enumerate(used)}
+        box_of, img_of, life, int_type = self._unique_masks(used)
+        group_boundaries, item_first, keys = {}, {}, []
+        item_off = np.zeros(n_groups + 1, np.int64)
+        boxes, ranges, lists = [], [], []
+        for g, group in enumerate(cc_groups):
+            if len(group) > 0:
+                b = [box_of[int(c)] for c in group]
+                bounds = (min(v[0] for v in b), max(v[1] for v in b), min(v[2] for v in b), max(v[3] for v in b))
+                group_boundaries[g] = tuple(int_type(v) for v in bounds)      # the reference's are the members' own integers
+                keys.append(g)
+                item_first[g] = len(boxes)
+                ages = group_ages[g]
+                for k in range(len(ages) - 1):
+                    t0, t1 = int(ages[k]), int(ages[k + 1])
+                    boxes.append(bounds)
+                    ranges.append((t0, t1))
+                    lists.append([slot[int(c)] for c in group if life[int(c)][0] <= t1 and t0 <= life[int(c)][1]])
+            item_off[g + 1] = len(boxes)
+        hist, owned = device.as_frame_history(binary_frames)
+        masks = None
+        try:
+            masks = device.GroupImages.from_host([box_of[c] for c in used], [img_of[c] for c in used], hist.width, hist.height, hist.lib)
+            gi, _ = hist.masked_images(masks, boxes, ranges, lists, float(segment_threshold), item_first=item_first)
+        finally:
+            if masks is not None:
+                masks.close()
+            if owned:
+                hist.close()
+        return device.LazyGroupImages(gi, item_off, groups=keys), group_boundaries
+
     def frames_from_groups(self, cc_groups, group_boundaries, groups_per_frame, group_ages, group_images, save_prefix=None,
                            stable_min_frames=3, show_unstable=True):
         return self._frames_png(png_device.codec())

@@ -26,7 +26,10 @@ each; (2) device: ONE overlaps call for all segments; (3) host: the component or
 it is sequential, order-dependent and a few hundred objects; (4) device: ONE render call for all keyframes.
 GenerateFromST3DForIntervals takes that route when the structure carries a live GroupImages (`_device_images`, set by
 LecturePipeline.finish(keyframes="device"), never pickled) or when LM_KEYFRAMES=device is set (read at every call, default
-"host"): then the images any segment selects are uploaded once (GroupImages.from_host)."""
+"host"): then the images any segment selects are uploaded once (GroupImages.from_host).
+
+KeyframeExtractor.extract (:146-222), the pixel history of the raw binary frames per video segment, runs on the frames as bit rows
+on the device (lecturemath_amd.device.FrameHistory): one pass per segment with bit-sliced counters."""
 import os
 
 import numpy as np
@@ -202,3 +205,39 @@ class KeyframeExtractor:
             keyframes.append(frame)
             keyframe_times.append(sorted(times))
         return keyframes, keyframe_times
+
+    @staticmethod
+    def extract(binary_images, video_segments, treshold_length, verbose=False, save_prefix=None):
+        """(:146-222) Per video segment (start, end) a dict: "sum" = per pixel the frames of the segment with ink, "age" = the index
+        of the first of them (0 where none), both float32; "filtered" = 255 where sum >= treshold_length; "local_max" = the
+        segment's frame with most ink (the first of equals: the reference replaces only on a strictly larger count).
+        binary_images: a list of uint8 0 / 255 frames, a device uint8 tensor [n, H, W], or a lecturemath_amd.device.FrameHistory
+        (used as it is).  local_max is the list's own array when a list was given, a host copy otherwise.  A segment holds at most
+        FrameHistory.MAX_RANGE frames; an empty or out-of-range segment raises ValueError.  save_prefix writes
+        <prefix>_filt_seg_<i + 1>.png."""
+        from lecturemath_amd import device, png
+        hist, owned = device.as_frame_history(binary_images)
+        out_segments = []
+        try:
+            for segment_idx, (start_int, end_int) in enumerate(video_segments):
+                if verbose:
+                    print("Processing segment #" + str(segment_idx))
+                start_int, end_int = int(start_int), int(end_int)
+                local_sum, local_age = hist.segment_stats(start_int, end_int, host=True)
+                best = start_int + int(np.argmax(hist.ink_counts(start_int, end_int - start_int + 1)))
+                if isinstance(binary_images, device.FrameHistory):
+                    local_max = hist.frame(best)
+                elif isinstance(binary_images, (list, tuple, np.ndarray)):
+                    local_max = binary_images[best]
+                else:
+                    local_max = hist.be.to_host(binary_images[best])
+                filtered_image = (local_sum >= treshold_length).astype(np.uint8) * 255
+                out_segments.append({"start": start_int, "end": end_int, "sum": local_sum, "age": local_age, "filtered": filtered_image,
+                                     "local_max": local_max})
+                if save_prefix is not None:
+                    with open(save_prefix + "_filt_seg_" + str(segment_idx + 1) + ".png", "wb") as f:
+                        f.write(png.encode_gray8(filtered_image).tobytes())
+        finally:
+            if owned:
+                hist.close()
+        return out_segments
