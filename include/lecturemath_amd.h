@@ -316,6 +316,31 @@ int lm_kf_pair_counts(LmKeyframes* kf, const int64_t* h_a_off, const int32_t* h_
                       const int32_t* h_b_items, const int32_t* h_disp, int n_q, int radius, int32_t* h_rows, int32_t* h_counts,
                       int64_t cap, int64_t* n_found, void* stream);
 
+/* ---- keyframes on the device -> CC table (csrc/lm_kfcc.hip) -----------------------------------------------------------------
+ * KeyFrameAnnotation.update_binary_cc (AccessMath/annotation/keyframe_annotation.py:139-146): the connected components of
+ * 255 - binary_image[:, :, 0] of every keyframe, as items of one table that owns its bits.  frames: n_frames keyframes of the
+ * context's width x height, pixel (y, x) of frame k is the byte at frames[((k * height + y) * width + x) * pixel_stride]
+ * (pixel_stride 3 reads channel 0 of [n][H][W][3] in place); a pixel is ink iff that byte is not 255.  on_device: `frames` and
+ * `masks` are device memory, else host memory (uploaded once).  Labelled in batches of the context's max_batch with
+ * scipy.ndimage.label's numbering (labeler.py:126); a CC is kept iff it has at least min_pixels pixels (update_binary_cc passes
+ * filter_small=False: 1).  Items: the kept CCs of frame 0 ascending by label, then frame 1, ...; then one full-frame item per mask
+ * (masks: [n_masks][height][width] bytes, non-zero = object; n_masks is 0 or n_frames).  Only two counts per frame and 32 bytes
+ * per CC cross to the host.  NULL (lm_last_error) on failure, nothing is left allocated; n_frames == 0 gives an empty table.
+ * Limit: fewer than 2^31 items.  Uses the context's run tables: not concurrently with other calls on `ctx`.  Synchronises. */
+LmKeyframes* lm_kf_create_from_frames(LmCtx* ctx, const uint8_t* frames, int on_device, int n_frames, int64_t pixel_stride,
+                                      const uint8_t* masks, int n_masks, int min_pixels, void* stream);
+/* The records of such a table: h_frame_off [n_frames + 1] (the CC items of frame f are h_frame_off[f] .. h_frame_off[f + 1]; mask k
+ * is item h_frame_off[n_frames] + k) and h_rec [n_cc][6] = cc_id, min_x, max_x, min_y, max_y, size with cc_id = label - 1 in the
+ * frame's UNFILTERED labelling (labeler.py:171-189).  Either pointer may be NULL.  HOST pointers.  LM_ERR_STATE for a table that
+ * was not made by lm_kf_create_from_frames. */
+int lm_kf_cc_records(const LmKeyframes* kf, int64_t* h_frame_off, int32_t* h_rec);
+/* The integer sums of Evaluator.compute_pixel_binary_metrics (AccessMath/evaluation/evaluator.py) for n pairs of keyframes of
+ * `pixels` pixels each, channel 0 read at a pixel stride like above: d_sums [n][4] = sum(255 - gt), sum(255 - summ),
+ * sum(255 - summ) where gt != 255, sum(255 - summ) where the mask is 0 (d_mask: [n][pixels] bytes or NULL = all zero).  Exact;
+ * the divisions by 255 stay with the caller in float64.  All pointers DEVICE.  Asynchronous on `stream`; n == 0 does nothing. */
+int lm_kf_pixel_sums(const uint8_t* d_gt, int64_t stride_gt, const uint8_t* d_summ, int64_t stride_summ, const uint8_t* d_mask, int n,
+                     int64_t pixels, uint64_t* d_sums, void* stream);
+
 /* ---- translation alignment of binary images (csrc/lm_align.hip) ------------------------------------------------------------
  * Aligner.computeTranslationAlignment (AccessMath/preprocessing/content/aligner.py:27-83), the first stage of the reference's
  * summary evaluation (Evaluator.keyframes_alignments, Evaluator.parallel_keyframe_align): for a pair of width x height images and

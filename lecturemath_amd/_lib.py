@@ -113,7 +113,10 @@ SIGNATURES = {
     "lm_kf_image": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _i64, _vp]),
     "lm_kf_crowded_tiles": (ctypes.c_int, [_vp, _vp, _vp]),
     "lm_kf_pair_counts": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _i64, _vp, _vp]),
-    "lm_align_create": (_vp, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
+    "lm_kf_create_from_frames": (_vp, [_vp, _vp, ctypes.c_int, ctypes.c_int, _i64, _vp, ctypes.c_int, ctypes.c_int, _vp]),
+    "lm_kf_cc_records": (ctypes.c_int, [_vp, _vp, _vp]),
+    "lm_kf_pixel_sums": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, ctypes.c_int, _i64, _vp, _vp]),
+    "lm_align_create":(_vp, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
     "lm_align_destroy": (None, [_vp]),
     "lm_align_set_images": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_int, _vp]),
     "lm_align_totals": (ctypes.c_int, [_vp, _vp, _vp]),

@@ -1440,4 +1440,5 @@ extern "C" int lm_stream_import_assign(LmStream* s, const void* d_in, int64_t by
 #include "lm_keyframes.hip"
 #include "lm_align.hip"
 #include "lm_ccmatch.hip"
+#include "lm_kfcc.hip"
 #include "lm_history.hip"

@@ -178,6 +178,10 @@ struct LmKeyframes {
     void* ws[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // grow-only scratch: join, bit tests, render, image,
     size_t ws_cap[6] = {0, 0, 0, 0, 0, 0};                                  // and the two of lm_kf_pair_counts (lm_ccmatch.hip)
     std::vector<char> stage[6];                 // host side of the uploads (alive until the next call)
+    // lm_kf_create_from_frames (lm_kfcc.hip): the CC items of frame f are cc_frame_off[f] .. cc_frame_off[f + 1], the masks follow
+    int from_frames = 0;
+    std::vector<int64_t> cc_frame_off;          // [n_frames + 1]
+    std::vector<int32_t> cc_rec;                // [n_cc][6] = cc_id, min_x, max_x, min_y, max_y, size
 };
 
 static void* lm_kf_scratch(LmKeyframes* kf, int slot, size_t bytes, const char* who)

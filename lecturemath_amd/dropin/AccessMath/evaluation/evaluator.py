@@ -54,8 +54,13 @@ except ImportError:
 
 
 def _pair_table(cc_lists, extra=(), width=0, height=0):
-    """device table of the CCs of `cc_lists` (and `extra` (box, image) items) in a frame that holds them all"""
+    """device table of the CCs of `cc_lists` (and `extra` (box, image) items) in a frame that holds them all.  CCs that already are
+    items of one live device.KeyframeCCs (lecturemath_amd.keyframes), unmoved, with extras that are masks of that table, are served
+    by a view of it: nothing is packed or uploaded.  Anything else -- host CCs, a CC moved by translateBox, two tables -- is uploaded."""
     from lecturemath_amd import device
+    view = device.KeyframeCCs.pair_view(cc_lists, extra)
+    if view is not None:
+        return view
     for lst in cc_lists:
         for cc in lst:
             width, height = max(width, cc.max_x + 1), max(height, cc.max_y + 1)
@@ -739,17 +744,24 @@ class Evaluator:
     @staticmethod
     def compute_pixel_binary_metrics(gt_frames, summary_frames):
         """pixel recall / precision / f-measure of the summary's binary keyframes against the ground truth's, keyframe by keyframe,
-        averaged; `board` leaves out the summary ink that lies on a ground-truth object"""
+        averaged; `board` leaves out the summary ink that lies on a ground-truth object.  Keyframes that live on the device
+        (lecturemath_amd.keyframes.DeviceKeyframe on both sides) get their four integer sums from one pass on the device
+        (lm_kf_pixel_sums); the divisions are the same float64 ones on the same uint64 values."""
+        from lecturemath_amd import keyframes as device_keyframes
+        device_sums = device_keyframes.pixel_sum_pairs(gt_frames, summary_frames)
         all_recall, all_precision, all_fmeasure, all_board_precision, all_board_fmeasure = [], [], [], [], []
         for idx, gt_frame in enumerate(gt_frames):
-            gt_ink = 255 - gt_frame.binary_image[:, :, 0]
-            summ_ink = 255 - summary_frames[idx].binary_image[:, :, 0]
-            total_gt = gt_ink.sum() / 255
-            total_summ = summ_ink.sum() / 255
-            total_correct = summ_ink[gt_ink > 0].sum() / 255
-            on_board = summ_ink.copy()
-            on_board[gt_frame.object_mask] = 0.0
-            total_board = on_board.sum() / 255
+            if device_sums is not None:
+                total_gt, total_summ, total_correct, total_board = (v / 255 for v in device_sums[idx])
+            else:
+                gt_ink = 255 - gt_frame.binary_image[:, :, 0]
+                summ_ink = 255 - summary_frames[idx].binary_image[:, :, 0]
+                total_gt = gt_ink.sum() / 255
+                total_summ = summ_ink.sum() / 255
+                total_correct = summ_ink[gt_ink > 0].sum() / 255
+                on_board = summ_ink.copy()
+                on_board[gt_frame.object_mask] = 0.0
+                total_board = on_board.sum() / 255
 
             recall = total_correct / total_gt
             precision = total_correct / total_summ

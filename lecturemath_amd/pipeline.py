@@ -104,13 +104,17 @@ class LecturePipeline:
         self._stamp(n, times, indices)
 
     # ---- steps 03, 04, 05 ----------------------------------------------------------------------------------------------
-    def finish(self, reconstructed_png=False, keyframes="host"):
+    def finish(self, reconstructed_png=False, keyframes="host", keyframe_ccs=False):
         """reconstructed_png: False (none), True (host zlib, whatever LM_PNG_CODEC says) or "device" (encoded on the device).
         keyframes: "host" expands every group image to host uint8 arrays for step 05 (the reference's data flow); "device" leaves
         them on the device as the bit rows step 03 wrote: step 05 reads them through a device.GroupImages view, st3d.cc_group_images
-        is a lazy read-only mapping over that view, and out["keyframes_device"] is the device tensor [n_segments, H, W, 3]."""
+        is a lazy read-only mapping over that view, and out["keyframes_device"] is the device tensor [n_segments, H, W, 3].
+        keyframe_ccs (with keyframes="device"): out["keyframe_ccs"] is the list of lecturemath_amd.keyframes.DeviceKeyframe over
+        keyframes_device, their connected components labelled on the device into one table (the summary evaluation's input)."""
         if keyframes not in ("host", "device"):
             raise ValueError("LecturePipeline.finish: keyframes must be 'host' or 'device', not %r" % (keyframes,))
+        if keyframe_ccs and keyframes != "device":
+            raise ValueError("LecturePipeline.finish: keyframe_ccs needs keyframes='device'")
         from AccessMath.data.space_time_struct import SpaceTimeStruct
         est, cfg = self.estimator, self.configuration
         est.finish_processing()
@@ -149,7 +153,12 @@ class LecturePipeline:
                 intervals = step04.process_input(self.process, step03)
             (summary_indices, summary_times, summary_keyframes), = _script("pre_ST3D_v3.0_05_generate_summary.py").process_input(self.process, [st3d, intervals])
         from AccessMath.preprocessing.content.keyframe_extractor import KeyframeExtractor   # noqa: F401  (cc_times below)
+        extra = {}
+        if keyframe_ccs:
+            from lecturemath_amd import keyframes as device_keyframes
+            extra["keyframe_ccs"] = device_keyframes.keyframes_from_frames(st3d._device_keyframes, idxs=summary_indices, times=summary_times,
+                                                                           lib=self.lib)
         return {"group_ages": group_ages, "conflicts": conflicts, "st3d": st3d, "intervals": intervals, "keyframes": summary_keyframes,
                 "keyframes_device": getattr(st3d, "_device_keyframes", None), "summary_indices": summary_indices, "summary_times": summary_times,
                 "reconstructed_png": compressed,
-                "reconstructed_device": lambda first, count: est.frames_from_groups_device(first, count)}
+                "reconstructed_device": lambda first, count: est.frames_from_groups_device(first, count), **extra}
