@@ -10,7 +10,7 @@
 //                             matches[dy + w][dx + w] = #{(y, x) : image i has ink at (y, x) and image j at (y - dy, x - dx)}
 //                         = sum over y of popcount(A[y] & shift(B[y - dy], dx))           (lm_k_align_match)
 // Everything is integer, so the counts do not depend on the order of the additions; the f-score, recall and precision the reference
-// derives from them are three divisions per displacement on the host (lecturemath_amd/device.py: TranslationAligner).
+// derives from them are three divisions per displacement on the host (lecturemath_amd/device/align.py: TranslationAligner).
 //
 // Limits (checked): W, H <= 32768 (the frame limit of lm_kf_*), hence H * W <= 2^30 and every count fits the int32 table;
 // window <= LM_ALIGN_MAX_WINDOW and <= min(W, H) (beyond that the reference's slices turn empty or misshapen and it raises).

@@ -1,5 +1,5 @@
 // lm_keyframes.hip -- step 05 (KeyframeExtractor.GenerateFromST3DForIntervals, AccessMath/preprocessing/content/
-// keyframe_extractor.py:13-145) on images that already are bit rows on the device.  Included by lm_api.hip.
+// keyframe_extractor.py:13-145) on images that already are bit rows on the device.  Included by lm_api.hip after lm_group.hip.
 //
 // LmKeyframes is a table of bit-row images placed in a W x H frame (LmBitImage: x0, y0, w, h, bits_off; ceil(w / 32) words per
 // row relative to the item's own x0 -- the layout of LmGroups::d_gbits and of lm_k_img_pack alike).  Two things are asked of it:

@@ -4,6 +4,8 @@
 //   regionCumulativeDistribution     accessmath_lib.c:113-173   contrast-limited, centred CDF of one image region
 //   adapthisteq                      accessmath_lib.c:175-329   CLAHE: per-tile CDFs + bilinear interpolation per pixel
 //   combine_results                  accessmath_lib.c:331-355   legacy binarizer: board mask + equalised image -> binary
+//   CC_AgeBoundaries                 accessmath_lib.c:357-413   per-label boxes, counts and ages (with lm_label_host, at the end of the file)
+// Included by lm_api.hip after lm_ctx.hip, whose context the last two stage their host pointers through.
 // These belong to the classical (pre-FCN) binarizers (binarizer.py:139-246, adaptive_equalizer.py:274-291), "next" row 4 of
 // SURVEY 8(f).  Pixel passes run on the device; the short float64 recurrences (256-bin CDF, per-column variance) are
 // finished on the host with the reference's own statement order, so results are bit-identical to the C library
@@ -311,4 +313,87 @@ extern "C" int speaker_detection_handle_frame(unsigned char* frame, unsigned cha
         change_deviation[1] = 0.0;
     }
     return total_changes;
+}
+
+// ------------------------------------------------------------------------------------------------
+// host-pointer convenience + the reference's own export (needs lm_ctx.hip: lm_ctx_create, lm_label_batch, lm_label_counts)
+// ------------------------------------------------------------------------------------------------
+static LmCtx* g_host_ctx = nullptr;
+
+static LmCtx* lm_host_ctx(int width, int height)
+{
+    if (g_host_ctx && (g_host_ctx->g.W != width || g_host_ctx->g.H != height)) {
+        lm_ctx_destroy(g_host_ctx);
+        g_host_ctx = nullptr;
+    }
+    if (!g_host_ctx) g_host_ctx = lm_ctx_create(width, height, 1);
+    return g_host_ctx;
+}
+
+static int lm_stage(LmCtx* c, size_t px)
+{
+    if (c->stage_px >= px) return LM_OK;
+    if (c->stage_u8) (void)hipFree(c->stage_u8);
+    if (c->stage_i32) (void)hipFree(c->stage_i32);
+    if (c->stage_f32) (void)hipFree(c->stage_f32);
+    c->stage_u8 = nullptr; c->stage_i32 = nullptr; c->stage_f32 = nullptr; c->stage_px = 0;
+    if (lm_alloc(&c->stage_u8, px) || lm_alloc(&c->stage_i32, px) || lm_alloc(&c->stage_f32, px)) return LM_ERR_HIP;
+    c->stage_px = px;
+    return LM_OK;
+}
+
+extern "C" int lm_label_host(const uint8_t* h_img, int width, int height, int32_t* h_labels)
+{
+    if (!h_img || !h_labels || width <= 0 || height <= 0) { lm_set_error("lm_label_host: bad arguments"); return -LM_ERR_ARG; }
+    LmCtx* c = lm_host_ctx(width, height);
+    if (!c) return -LM_ERR_HIP;
+    const size_t px = (size_t)width * height;
+    if (lm_stage(c, px)) return -LM_ERR_HIP;
+    if (hipMemcpy(c->stage_u8, h_img, px, hipMemcpyHostToDevice) != hipSuccess) { lm_set_error("lm_label_host: H2D failed"); return -LM_ERR_HIP; }
+    int rc = lm_label_batch(c, c->stage_u8, 1, c->stage_i32, nullptr);
+    if (rc) return -rc;
+    int32_t n = 0;
+    rc = lm_label_counts(c, &n, nullptr);
+    if (rc) return -rc;
+    if (hipMemcpy(h_labels, c->stage_i32, px * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) { lm_set_error("lm_label_host: D2H failed"); return -LM_ERR_HIP; }
+    return n;
+}
+
+// accessmath_lib.c:357-413.  Always returns 0 like the reference (callers ignore the value, labeler.py:166);
+// a failure is reported through lm_last_error() and leaves the outputs in their initial state.
+extern "C" int CC_AgeBoundaries(int* labels, float* ages, int width, int height, int count_labels, int* out_mins_y,
+                                int* out_maxs_y, int* out_mins_x, int* out_maxs_x, int* out_counts, float* output_age)
+{
+    if (count_labels <= 0 || width <= 0 || height <= 0) return 0;
+    LmCtx* c = lm_host_ctx(width, height);
+    const size_t px = (size_t)width * height;
+    if (!c || lm_stage(c, px)) return 0;
+    const int n = count_labels;
+    int32_t* d_out = nullptr;     // 9 arrays of n
+    if (hipMalloc((void**)&d_out, (size_t)n * 9 * sizeof(int32_t)) != hipSuccess) { lm_set_error("CC_AgeBoundaries: hipMalloc failed"); return 0; }
+    int32_t *mny = d_out, *mxy = d_out + n, *mnx = d_out + 2 * (size_t)n, *mxx = d_out + 3 * (size_t)n, *cnt = d_out + 4 * (size_t)n,
+            *ageb = d_out + 5 * (size_t)n, *last_px = d_out + 7 * (size_t)n, *last_neg = d_out + 8 * (size_t)n;
+    float* agef = (float*)(d_out + 6 * (size_t)n);
+    bool ok = hipMemcpy(c->stage_i32, labels, px * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && ages) ok = hipMemcpy(c->stage_f32, ages, px * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        const float* d_ages = ages ? c->stage_f32 : (const float*)nullptr;
+        hipLaunchKernelGGL(lm_k_ab_init, dim3(lm_blocks(n, 256)), dim3(256), 0, (hipStream_t)0, mny, mxy, mnx, mxx, cnt, ageb, last_px, last_neg,
+                           width, height, n);
+        hipLaunchKernelGGL(lm_k_ab_scan, dim3(lm_blocks((long long)px, 256)), dim3(256), 0, (hipStream_t)0, c->stage_i32, d_ages, width, height, n,
+                           mny, mxy, mnx, mxx, cnt, last_px, last_neg);
+        hipLaunchKernelGGL(lm_k_ab_age, dim3(lm_blocks((long long)px, 256)), dim3(256), 0, (hipStream_t)0, c->stage_i32, d_ages, width, height, n,
+                           last_neg, ageb);
+        hipLaunchKernelGGL(lm_k_ab_finish, dim3(lm_blocks(n, 256)), dim3(256), 0, (hipStream_t)0, ageb, last_px, last_neg, d_ages, agef, n);
+        const size_t nb = (size_t)n * sizeof(int32_t);
+        ok = hipMemcpy(out_mins_y, mny, nb, hipMemcpyDeviceToHost) == hipSuccess &&
+             hipMemcpy(out_maxs_y, mxy, nb, hipMemcpyDeviceToHost) == hipSuccess &&
+             hipMemcpy(out_mins_x, mnx, nb, hipMemcpyDeviceToHost) == hipSuccess &&
+             hipMemcpy(out_maxs_x, mxx, nb, hipMemcpyDeviceToHost) == hipSuccess &&
+             hipMemcpy(out_counts, cnt, nb, hipMemcpyDeviceToHost) == hipSuccess &&
+             hipMemcpy(output_age, agef, nb, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (!ok) lm_set_error("CC_AgeBoundaries: device copy/launch failed");
+    (void)hipFree(d_out);
+    return 0;
 }
